@@ -21,6 +21,9 @@ and the texture pyramid stored in fp16 under autocast (BASELINE configs[4]).  (N
 BASELINE.json configs[k-1].)
 
 Rank 0 prints ONE JSON line.  `value` = all ranks' pixels / max-over-ranks wall time of the K timed steps.
+A plain run sets up, warms up, times the K steps and prints the line; everything below is measured only with `--full`.
+`--dump-outputs DIR` writes what the last timed step computed (loss, the images the loss is made of, the shared
+gradients; larger arrays as a fixed, seeded sample) as DIR/<name>.npy, so that two builds can be compared output for output.
 `roofline` prices the single HIP kernel with the largest average duration: SURVEY.md 8d's algorithmic bytes of the
 tensors that kernel streams / its HIP-event time, measured live through the library's per-kernel timing
 (drtk_amd_kernel_timing_*: a pair of HIP events around every launch, on the stream it is launched on) over extra
@@ -66,9 +69,14 @@ def parse():
     ap.add_argument("--res", type=int, default=None)
     ap.add_argument("--channels", type=int, default=None)
     ap.add_argument("--tex", type=int, default=4096, help="textured workload: texture size")
-    ap.add_argument("--cpu-sample-views", type=int, default=None, help="views timed on the CPU (0 = skip)")
-    ap.add_argument("--kernel-steps", type=int, default=5, help="extra steps run under the per-kernel HIP-event timing")
-    ap.add_argument("--no-graph", action="store_true", help="skip the captured-graph timing of the same step")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel roofline, CPU baseline, captured graph, "
+                         "interpolate_masked / operators-only / flat_zero variants, collective timings")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64, a seeded sample of large ones)")
+    ap.add_argument("--cpu-sample-views", type=int, default=None, help="--full: views timed on the CPU (0 = skip)")
+    ap.add_argument("--kernel-steps", type=int, default=5, help="--full: extra steps run under the per-kernel HIP-event timing")
+    ap.add_argument("--no-graph", action="store_true", help="--full: skip the captured-graph timing of the same step")
     ap.add_argument("--reduce-after-backward", action="store_true",
                     help="N > 1: ONE all-reduce of all shared gradients after the backward pass instead of one per shared tensor launched from inside it (A/B of the overlap)")
     ap.add_argument("--grad-reset", default="auto", choices=["auto", "set_to_none", "flat_zero"],
@@ -308,6 +316,29 @@ def emit_line(obj):
     os.write(_JSON_FD, (json.dumps(obj) + "\n").encode())
 
 
+DUMP_SAMPLE = 1 << 20      # elements kept of a larger output
+DUMP_BUDGET = 64 << 20     # bytes of all files together
+
+
+def dump_outputs(out_dir, arrays):
+    """`--dump-outputs`: every array as out_dir/<name>.npy, integers and doubles as float64 (exact for int32 indices), the
+    rest as float32.  An array of more than DUMP_SAMPLE elements is replaced by DUMP_SAMPLE of its flattened elements at
+    positions drawn with a fixed seed -- the same positions for every array of the same size, in every run."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            idx = th.randint(t.numel(), (DUMP_SAMPLE,), generator=th.Generator().manual_seed(0)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.to(th.float64 if t.dtype in (th.float64, th.int32, th.int64) else th.float32).cpu().numpy()
+        total += a.nbytes
+        assert total <= DUMP_BUDGET, f"--dump-outputs: more than {DUMP_BUDGET} bytes"
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def timed_loop(step, steps, dev, world):
     """The contract's timing: barrier + synchronize, EXACTLY `steps` steps, barrier + synchronize, wall clock, MAX over
     ranks.  Beside it every step lies between two HIP events on the stream the step runs on (hipEvent,
@@ -425,7 +456,7 @@ def main():
 
     grad_reset = args.grad_reset if args.grad_reset != "auto" else ("flat_zero" if grouped else "set_to_none")
 
-    def step(fused_mask=False, reduce=True, flat_zero=None):
+    def step(fused_mask=False, reduce=True, flat_zero=None, keep=None):
         for r in reducers:
             r.enabled = reduce  # off: this rank steps alone (no collective may be entered, not even from a gradient hook)
         if flat_zero is None:
@@ -445,6 +476,7 @@ def main():
                 out = S.textured_shading(drtk_amd, v_world[None].expand(n_local, -1, -1), v_pix, vi, up(vt).expand(n_local, -1, -1), vti,
                                          [up(t).expand(n_local, -1, -1, -1) for t in tex], campos, camrot, focal, H, W)
             img, depth_img = out["img"], out["depth_img"]
+            index_img, bary_img = out["index_img"], out["bary_img"]
         else:
             a = attr.expand(n_local, -1, -1)
             index_img = drtk_amd.rasterize(v_pix, vi, H, W)
@@ -463,18 +495,36 @@ def main():
         if reduce:
             for r in reducers:
                 r.finish()
+        if keep is not None:
+            keep.update(loss=loss, index_img=index_img, depth_img=depth_img, bary_img=bary_img, img=img)
         return loss
 
     if args.graph_child:
         return graph_child(step, leaves, args.steps, n_total * H * W)
     for _ in range(args.warmup):
         step()
-    elapsed, loss = timed_loop(step, args.steps, dev, 2 if grouped else 1)
+    outputs, timed_step = {}, step
+    if args.dump_outputs:
+        done = [0]
+
+        def timed_step():  # the last timed step keeps its outputs
+            done[0] += 1
+            return step(keep=outputs if done[0] == args.steps else None)
+
+    elapsed, loss = timed_loop(timed_step, args.steps, dev, 2 if grouped else 1)
     median_step_ms = timed_loop.last_median_ms
     ms_per_step = elapsed / args.steps * 1e3
     mpix = n_total * H * W * args.steps / elapsed / 1e6
+    if args.dump_outputs and rank == 0:
+        # the shared gradients as the step left them (later steps of --full overwrite them)
+        if textured:
+            outputs.update(grad_v_world=v_world.grad, grad_vt=vt.grad, grad_tex=th.cat([t.grad.reshape(-1).float() for t in tex]))
+        else:
+            outputs.update(grad_v_world=v_world.grad, grad_attr=attr.grad)
+        dump_outputs(args.dump_outputs, outputs)
+    outputs.clear()
     comm = None
-    if grouped:
+    if grouped and args.full:
         # the collectives' own times come from ONE extra step with the reducers' event bracketing on (every rank runs it);
         # the timed region above runs without those events
         for r in reducers:
@@ -491,7 +541,7 @@ def main():
     # buffer and accumulate into it.  So that a scaling curve can be read like for like, the one-GPU line also carries the
     # SAME step timed the group's way (no collective: there is no group)
     flat_zero_alt = None
-    if not grouped and grad_reset == "set_to_none":
+    if args.full and not grouped and grad_reset == "set_to_none":
         step(flat_zero=True)
         el_fz, _ = timed_loop(lambda: step(flat_zero=True), args.steps, dev, world)
         flat_zero_alt = {"note": "the same step with the shared gradients zeroed in the reducer's flat buffer and accumulated into it -- what "
@@ -501,7 +551,7 @@ def main():
 
     # the same step with the drtk_amd.interpolate_masked extension (reported beside, never as `value`)
     ext = None
-    if not textured:
+    if args.full and not textured:
         step(True)
         elapsed_fused, loss_fused = timed_loop(lambda: step(True), args.steps, dev, world)
         ext = {"interpolate_masked": {
@@ -512,7 +562,7 @@ def main():
 
     # the operators alone (reference API, wall clock): the same forward, and a backward pass seeded with RESIDENT upstream
     # gradients instead of the user-side mask and loss -- what the step costs without the PyTorch glue around the path
-    if not textured and world == 1:
+    if args.full and not textured and world == 1:
         gsrc = th.Generator(device=dev).manual_seed(1)
         with th.no_grad():
             v_pix0 = transform(v_world[None], campos, camrot, focal, princpt)
@@ -549,7 +599,7 @@ def main():
     # Measured in a fresh CHILD process (started here, never exec'ed over this one) while this process idles: a capture
     # that goes wrong takes down the process it runs in, and the headline must not depend on it.
     graph = None
-    if world == 1 and not grouped and not args.no_graph:
+    if args.full and world == 1 and not grouped and not args.no_graph:
         import subprocess
 
         th.cuda.synchronize()
@@ -563,8 +613,8 @@ def main():
         except Exception as e:
             graph = {"error": f"{type(e).__name__}: {e}"[:300]}
 
-    result = None
-    if rank == 0:
+    result = roofline = path = cpu = None
+    if args.full and rank == 0:
         # ---- per-kernel HIP-event timing of the real step (library kernels only; PyTorch glue is t_step - t_ops).
         # Rank 0 alone runs these steps, so with several ranks they must not enter a collective.
         alone = world == 1
@@ -687,7 +737,6 @@ def main():
             "ops_ms": ops_ms,
             "kernels": kernels,
         }
-        cpu = None
         if world == 1 and args.cpu_sample_views > 0:
             with th.no_grad():
                 v_pix = transform(v_world[None].expand(n_local, -1, -1), campos, camrot, focal, princpt).contiguous()
@@ -696,6 +745,7 @@ def main():
             else:
                 a_full = attr.detach().expand(n_local, -1, -1).contiguous()
                 cpu = cpu_baseline(v_pix, vi, a_full, H, W, min(args.cpu_sample_views, n_local))
+    if rank == 0:
         if textured:
             what = (f"{n_local} views/GPU x {world} GPU, {args.mesh}-tri UV-sphere scene (F={vi.shape[0]}, V={v_world.shape[0]}), {H}x{W}, "
                     f"RGB texture {args.tex}^2 + {len(tex) - 1} mip levels and uv attributes stored in fp16 under autocast, "
@@ -741,6 +791,9 @@ def main():
             "path_roofline": path,
             "cpu_baseline": cpu,
         }
+        if not args.full:  # measured only with --full
+            for k in ("all_reduce", "graph_step", "extensions", "roofline", "path_roofline", "cpu_baseline"):
+                del result[k]
         emit_line(result)
     if grouped:
         th.distributed.barrier()

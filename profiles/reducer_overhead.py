@@ -26,5 +26,5 @@ if stub:
         return _Done() if async_op else None
 
     dist.all_reduce = fake
-sys.argv = ["bench.py", "--no-graph", "--cpu-sample-views", "0", "--kernel-steps", "1"]
+sys.argv = ["bench.py", "--full", "--no-graph", "--cpu-sample-views", "0", "--kernel-steps", "1"]
 runpy.run_path(os.path.join(ROOT, "bench.py"), run_name="__main__")

@@ -14,7 +14,7 @@ cp gpurun_out/round/bench_n1.json gpurun_out/round/bench_step_kernel_stats.txt g
 bash profiles/scripts/other_configs.sh > $F/other_configs.log 2>&1
 mkdir -p $F/other_configs; cp gpurun_out/configs/*.json $F/other_configs/
 python3 profiles/shape_bench.py --reps 10 --channels 4,8,12,16,20,24,32,40,64 --split-dir $F > $F/shape_bench.json 2> $F/shape_bench.log
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $F/tex_stats -- python3 bench.py --workload textured --no-graph --steps 10 --warmup 2 --cpu-sample-views 0 > $F/tex_stats.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $F/tex_stats -- python3 bench.py --full --workload textured --no-graph --steps 10 --warmup 2 --cpu-sample-views 0 > $F/tex_stats.log 2>&1
 python3 profiles/summarize_stats.py $F/tex_stats $F/textured_step_kernel_stats.txt > /dev/null 2>&1
 rm -rf $F/tex_stats
 ( for c in 3 8 16; do python3 profiles/mipmap_bench.py --reps 5 --channels $c 2>&1 | grep "flags="; done; python3 profiles/mipmap_bench.py --reps 5 --channels 3 --bicubic 2>&1 | grep "flags=" ) > $F/mipmap_by_C.txt

@@ -26,7 +26,7 @@ DRTK_CAPI_NO_INTERP_WS=1 python3 profiles/shape_bench.py --what interp_c --reps 
 python3 profiles/shape_bench.py --what raster,f64 --reps 10 --split-dir $F > $F/shape_bench.json 2> $F/shape_bench.log
 ( python3 profiles/kernel_bench.py --only interpolation_matrix_kernel_only,interpolation_matrix,interpolation_matrix_backward,normal_matrix_values,normal_matrix_values_backward,rasterize_wireframe,rasterize --reps 5 2>&1 | grep -v amdgpu.ids
   echo "--mesh 250k"; python3 profiles/kernel_bench.py --only interpolation_matrix_kernel_only,normal_matrix_values,normal_matrix_values_backward,rasterize_wireframe,rasterize --mesh 250k --reps 5 2>&1 | grep -v amdgpu.ids ) > $F/sparse_and_wireframe.txt
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $F/tex_stats -- python3 bench.py --workload textured --no-graph --steps 10 --warmup 2 --cpu-sample-views 0 > $F/tex_stats.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $F/tex_stats -- python3 bench.py --full --workload textured --no-graph --steps 10 --warmup 2 --cpu-sample-views 0 > $F/tex_stats.log 2>&1
 python3 profiles/summarize_stats.py $F/tex_stats $F/textured_step_kernel_stats.txt > /dev/null 2>&1
 rm -rf $F/tex_stats
 ( for c in 3 8 16; do python3 profiles/mipmap_bench.py --reps 5 --channels $c 2>&1 | grep "flags="; done
@@ -34,7 +34,7 @@ rm -rf $F/tex_stats
   python3 profiles/mipmap_bench.py --reps 5 --channels 3 --bicubic 2>&1 | grep "flags=" ) > $F/mipmap_by_C.txt
 ( python3 profiles/mipmap_bench.py --reps 3 --f64 2>&1 | grep "flags="; python3 profiles/mipmap_bench.py --reps 3 --f64 --bicubic 2>&1 | grep "flags="; python3 profiles/mipmap_bench.py --reps 3 --f64 --channels 8 2>&1 | grep "flags=" ) > $F/mipmap_f64.txt
 ( for sc in 1.0 4.0; do echo "kernel_bench --uvscale $sc"; python3 profiles/kernel_bench.py --only mipmap_fwd,mipmap_bwd --reps 5 --uvscale $sc 2>&1 | grep -i "mipmap"; done ) > $F/mipmap_minified.txt
-timeout 300 rocprofv3 --kernel-trace --output-format csv -d $F/trace_eager -- python3 bench.py --no-graph --cpu-sample-views 0 --steps 8 --warmup 3 > $F/trace_eager.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --output-format csv -d $F/trace_eager -- python3 bench.py --full --no-graph --cpu-sample-views 0 --steps 8 --warmup 3 > $F/trace_eager.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --output-format csv -d $F/trace_graph -- python3 bench.py --graph-child --steps 8 > $F/trace_graph.log 2>&1
 python3 profiles/trace_gaps.py $F/trace_eager $F/trace_graph --steps 5 > $F/graph_vs_eager.txt 2>&1
 rm -rf $F/trace_eager $F/trace_graph

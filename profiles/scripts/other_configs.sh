@@ -4,7 +4,7 @@ export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/configs
 rm -rf $OUT; mkdir -p $OUT
-run() { name=$1; shift; timeout 400 python3 bench.py --steps ${STEPS:-10} --warmup 3 --cpu-sample-views 0 "$@" 2> $OUT/$name.err | grep "^{" > $OUT/$name.json; }
+run() { name=$1; shift; timeout 400 python3 bench.py --full --steps ${STEPS:-10} --warmup 3 --cpu-sample-views 0 "$@" 2> $OUT/$name.err | grep "^{" > $OUT/$name.json; }
 STEPS=200 run config2_10k_512_v4_c3 --config 2   # a 0.4 ms step: ten of them are shorter than one scheduler hiccup
 run config3_100k_2048_v8_c16      --config 3
 run config4_250k_2048_v8_c16      --config 4

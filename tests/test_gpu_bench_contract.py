@@ -16,7 +16,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--mesh", "10k", "--res", "512", "--views", "2", "--channels", "3", "--steps", "3", "--warmup", "1", "--kernel-steps", "2"]
+SMALL = ["--mesh", "10k", "--res", "512", "--views", "2", "--channels", "3", "--steps", "3", "--warmup", "1", "--kernel-steps", "2", "--full"]
 TOP = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
        "dtype", "data", "config", "roofline", "cpu_baseline"}
 
@@ -115,7 +115,7 @@ def test_gpus_flag_must_match_the_process_group():
 def test_textured_workload_line():
     """`--workload textured` (BASELINE configs[4] in small): same contract, its own metric string, fp16-stored leaves."""
     d = _run([sys.executable, "bench.py", "--workload", "textured", "--mesh", "10k", "--res", "512", "--tex", "512", "--views", "2",
-              "--steps", "3", "--warmup", "1", "--kernel-steps", "2", "--cpu-sample-views", "1"])
+              "--steps", "3", "--warmup", "1", "--kernel-steps", "2", "--cpu-sample-views", "1", "--full"])
     assert TOP <= set(d) and "textured" in d["metric"] and "fp16" in d["config"]["workload"]
     ks = d["path_roofline"]["kernels"]
     for k in ("uv_derivative_kernel", "mipmap_forward_lean_kernel", "mipmap_backward_lean_kernel", "tile_raster_kernel", "edge_dots_kernel"):
@@ -152,3 +152,51 @@ def test_one_rank_process_group_over_rccl():
     assert ar is not None and ar["collectives_per_step"] == 2 and ar["staging_dtype"] == "float32"
     assert ar["bytes"] == 4 * d["config"]["vertices"] * (3 + d["config"]["channels"])
     assert ar["ms_launch_to_done"] > 0 and ar["ms_exposed_on_main_stream"] >= 0
+
+
+def test_plain_run_is_lean_and_dumps_its_last_step(tmp_path):
+    """Without --full the line carries the headline alone (none of the extra measurements), --steps is the number of timed
+    steps, and --dump-outputs writes what the last timed step computed: float32 / float64 .npy files, 64 MB at most.  Two
+    runs with the same workload start from the same inputs, so whatever their step counts their last steps agree."""
+    import numpy as np
+
+    lean = ["--mesh", "10k", "--res", "512", "--views", "2", "--channels", "3", "--warmup", "1"]
+    runs = []
+    for steps in (2, 5):
+        out = tmp_path / f"steps{steps}"
+        d = _run([sys.executable, "bench.py", *lean, "--steps", str(steps), "--dump-outputs", str(out)])
+        assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "loss"} <= set(d)
+        assert not {"roofline", "path_roofline", "cpu_baseline", "graph_step", "extensions", "all_reduce"} & set(d)
+        assert d["steps"] == steps and d["ms_per_step"] > 0 and d["unit"] == "Mpix/s" and d["dtype"] == "f32"
+        px = d["config"]["views_per_gpu"] * d["config"]["height"] * d["config"]["width"]
+        assert abs(d["value"] - px / (d["ms_per_step"] * 1e-3) / 1e6) <= 1e-3 * d["value"]
+        files = {f.stem: np.load(f) for f in out.glob("*.npy")}
+        assert set(files) == {"loss", "index_img", "depth_img", "bary_img", "img", "grad_v_world", "grad_attr"}
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+        assert sum(a.nbytes for a in files.values()) <= 64 << 20
+        assert abs(float(files["loss"]) - d["loss"]) <= 1e-5 * max(1.0, abs(d["loss"]))
+        assert files["index_img"].shape == (2, 512, 512) and files["grad_attr"].shape == (1, d["config"]["vertices"], 3)
+        assert files["img"].shape == (1 << 20,)  # 2 x 3 x 512 x 512 elements: a seeded sample
+        runs.append(files)
+    a, b = runs
+    for name in ("index_img", "depth_img", "bary_img"):
+        assert np.array_equal(a[name], b[name]), name
+    for name in ("loss", "img", "grad_v_world", "grad_attr"):
+        tol = 1e-5 + 1e-5 * float(np.abs(b[name]).max())
+        assert float(np.abs(a[name].astype(np.float64) - b[name]).max()) <= tol, name
+
+
+def test_plain_textured_run_dumps_its_outputs(tmp_path):
+    """--dump-outputs on the textured workload: the fp16-stored leaves' gradients are written too (the whole texture
+    pyramid's as one sampled array), all in float32 / float64 within 64 MB."""
+    import numpy as np
+
+    d = _run([sys.executable, "bench.py", "--workload", "textured", "--mesh", "10k", "--res", "512", "--tex", "512", "--views", "2",
+              "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    assert "textured" in d["metric"] and d["steps"] == 2 and d["ms_per_step"] > 0 and "roofline" not in d
+    files = {f.stem: np.load(f) for f in tmp_path.glob("*.npy")}
+    assert set(files) == {"loss", "index_img", "depth_img", "bary_img", "img", "grad_v_world", "grad_vt", "grad_tex"}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    assert abs(float(files["loss"]) - d["loss"]) <= 1e-5 * max(1.0, abs(d["loss"]))
+    assert files["grad_vt"].shape[-1] == 2 and float(np.abs(files["grad_tex"]).max()) > 0

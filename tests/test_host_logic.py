@@ -616,33 +616,30 @@ print("ok")
         assert f" T PyInit_{ext}" in syms  # rasterize_module.cpp:73-75
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/drtk"), reason="build container only: needs the reference's Python package")
-def test_reference_python_package_runs_on_top_of_our_extension_modules(tmp_path):
-    """The *_ext surface as the reference's own Python sees it: a package directory made of LINKS to the reference's
-    drtk/*.py (nothing copied) plus our drtk/<name>_ext.so imports, resolves its operators in our library, and a call
-    through the reference's wrapper arrives in our operator (CPU tensors: the 'HIP path only' error of the CPU key)."""
+def test_a_package_of_links_reaches_our_operators_the_way_the_reference_wrappers_call_them(tmp_path):
+    """The *_ext surface as a DRTK-style package elsewhere sees it: a package directory holding nothing but LINKS to our
+    drtk/<name>_ext.so and a loader that does what the reference's drtk/utils/load_torch_ops.py:14-20 does (import the
+    module, th.ops.load_library its file) resolves every operator in our library, and the calls of the reference's
+    wrappers (rasterize.py:64, render.py:38, interpolate.py:50, edge_grad_estimator.py:174) with CPU tensors arrive in
+    our operator (the 'HIP path only' error of the CPU key)."""
     pkg = tmp_path / "drtk"
     pkg.mkdir()
-    ref = "/root/reference/drtk"
-    for f in os.listdir(ref):
-        if f.endswith(".py"):
-            os.symlink(os.path.join(ref, f), pkg / f)
-    os.symlink(os.path.join(ref, "utils"), pkg / "utils")
-    for ext in ("rasterize_ext", "render_ext", "interpolate_ext", "edge_grad_ext", "mipmap_grid_sampler_ext"):
+    exts = ("rasterize_ext", "render_ext", "interpolate_ext", "edge_grad_ext", "mipmap_grid_sampler_ext")
+    for ext in exts:
         os.symlink(os.path.join(ROOT, "drtk", ext + ".so"), pkg / (ext + ".so"))
+    (pkg / "__init__.py").write_text("import importlib\nimport torch as th\n\nfor _ext in %r:\n"
+                                     "    th.ops.load_library(importlib.import_module(__name__ + '.' + _ext).__file__)\n" % (exts,))
     out = _run_py("""
-import builtins, sys, types
-# the reference also wants grid_scatter_ext / msi_ext / filter2d_ext, which are out of scope: tolerated the way its
-# documentation build tolerates a missing extension (drtk/utils/load_torch_ops.py:22-26)
-builtins.__sphinx_build__ = True
-sys.modules.setdefault("sphinx", types.ModuleType("sphinx"))
-import torch as th, drtk
-assert drtk.__file__.startswith(sys.argv[-1] if False else drtk.__file__) and "/root/repo/drtk/" not in drtk.__file__
-assert "site-packages" not in drtk.rasterize_ext.__file__ if hasattr(drtk, "rasterize_ext") else True
-v = th.zeros(1, 3, 3); vi = th.zeros(1, 3, dtype=th.int32)
-for call in (lambda: drtk.rasterize(v, vi, 8, 8), lambda: drtk.render(v, vi, th.zeros(1, 8, 8, dtype=th.int32)),
-             lambda: drtk.interpolate(v, vi, th.zeros(1, 8, 8, dtype=th.int32), th.zeros(1, 3, 8, 8)),
-             lambda: drtk.edge_grad_estimator(v, vi, th.zeros(1, 3, 8, 8), th.zeros(1, 3, 8, 8), th.zeros(1, 8, 8, dtype=th.int32))):
+import os, sys, torch as th, drtk
+here = os.path.dirname(drtk.__file__)
+for ext, op in [("rasterize_ext", "rasterize"), ("render_ext", "render"), ("interpolate_ext", "interpolate"),
+                ("edge_grad_ext", "edge_grad_estimator"), ("mipmap_grid_sampler_ext", "mipmap_grid_sampler_2d")]:
+    assert os.path.dirname(sys.modules["drtk." + ext].__file__) == here, sys.modules["drtk." + ext].__file__
+    assert th._C._dispatch_has_kernel_for_dispatch_key(ext + "::" + op, "CUDA"), op
+v = th.zeros(1, 3, 3); vi = th.zeros(1, 3, dtype=th.int32); index = th.zeros(1, 8, 8, dtype=th.int32); img = th.zeros(1, 3, 8, 8)
+for call in (lambda: th.ops.rasterize_ext.rasterize(v, vi, 8, 8, False), lambda: th.ops.render_ext.render(v, vi, index),
+             lambda: th.ops.interpolate_ext.interpolate(v, vi, index, img),
+             lambda: th.ops.edge_grad_ext.edge_grad_estimator(v, img, vi, img, index, 1e4)):
     try:
         call(); raise SystemExit("CPU call did not raise")
     except RuntimeError as e:
@@ -723,3 +720,31 @@ def test_bench_flags_a_stale_traffic_collection(tmp_path, monkeypatch):
     table, path = bench.measured_traffic_table()
     assert path is None or len(table) > 0
     assert '"sources": sources' in open(os.path.join(ROOT, "profiles", "make_traffic.py")).read()
+
+
+def test_bench_dump_outputs_writes_float_arrays_and_samples_large_ones_the_same_way(tmp_path):
+    """bench.py --dump-outputs (host logic, CPU tensors): small arrays keep their shape and values, integers become float64,
+    half becomes float32, and an array above DUMP_SAMPLE elements becomes DUMP_SAMPLE elements taken at seeded positions
+    -- the same positions in every call, so two runs (two builds) can be compared element for element."""
+    import importlib.util
+
+    import numpy as np
+
+    spec = importlib.util.spec_from_file_location("_bench_for_dump_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    big = th.arange(3 * bench.DUMP_SAMPLE, dtype=th.float32).reshape(3, -1)
+    arrays = dict(loss=th.tensor(1.5), index=th.tensor([[-1, 7], [2 ** 30, 3]], dtype=th.int32),
+                  half=th.tensor([0.5, 2.0], dtype=th.float16), big=big)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    a = {f.stem: np.load(f) for f in (tmp_path / "a").glob("*.npy")}
+    b = {f.stem: np.load(f) for f in (tmp_path / "b").glob("*.npy")}
+    assert set(a) == set(arrays) and all(np.array_equal(a[k], b[k]) for k in a)
+    assert a["loss"].dtype == np.float32 and a["loss"].shape == () and float(a["loss"]) == 1.5
+    assert a["index"].dtype == np.float64 and a["index"].tolist() == [[-1, 7], [2 ** 30, 3]]
+    assert a["half"].dtype == np.float32 and a["half"].tolist() == [0.5, 2.0]
+    s = a["big"]
+    assert s.dtype == np.float32 and s.shape == (bench.DUMP_SAMPLE,)
+    assert np.all(np.diff(s) >= 0) and len(np.unique(s)) > bench.DUMP_SAMPLE // 2  # sorted positions, spread over the array
+    assert s.min() < bench.DUMP_SAMPLE and s.max() >= 2 * bench.DUMP_SAMPLE
