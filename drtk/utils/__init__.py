@@ -1,9 +1,11 @@
-"""drtk.utils of the drop-in: the loader and the pinhole projection (drtk/utils/__init__.py:8-22 restricted to the
-path); the mesh-geometry helpers (face_dpdt, face_info, vert_normals, vert_binormals, index) are outside it."""
+"""drtk.utils of the drop-in: the loader, the pinhole projection and the mesh geometry (drtk/utils/__init__.py:8-22 of
+the reference); project_points_grad is outside it."""
+from drtk.utils.geometry import face_dpdt, face_info, vert_binormals, vert_normals  # noqa: F401
+from drtk.utils.indexing import index  # noqa: F401
 from drtk.utils.load_torch_ops import load_torch_ops  # noqa: F401
 from drtk.utils.projection import DISTORTION_MODES, project_pinhole, project_points  # noqa: F401
 
-_OUT_OF_SCOPE = {"face_dpdt", "face_info", "vert_binormals", "vert_normals", "index", "project_points_grad"}
+_OUT_OF_SCOPE = {"project_points_grad"}
 
 
 def __getattr__(name):

@@ -1,8 +1,16 @@
 """drtk_amd -- MI355X-native differentiable rasterization hot path
 (rasterize -> render -> interpolate -> edge_grad), drop-in for the `drtk.*` functions of
-facebookresearch/DRTK on PyTorch-ROCm.  Kernels: hand-written HIP for gfx950 in
+facebookresearch/DRTK on PyTorch-ROCm, plus the mesh geometry of `drtk.utils` (vertex normals,
+face info, UV Jacobians, binormals).  Kernels: hand-written HIP for gfx950 in
 `drtk_amd/csrc`, C ABI in `include/drtk_amd.h`."""
 from drtk_amd.edge_grad_estimator import edge_grad_estimator  # noqa: F401
+from drtk_amd.geometry import (  # noqa: F401
+    face_attribute_to_vert,
+    face_dpdt,
+    face_info,
+    vert_binormals,
+    vert_normals,
+)
 from drtk_amd.graph import capture_step  # noqa: F401
 from drtk_amd.interpolate import (  # noqa: F401
     interpolate,
@@ -21,7 +29,8 @@ __version__ = "0.1.0"
 # The public surface.  Same names, arguments and defaults as `drtk.*` for everything on the hot path and its "next"
 # rows; `interpolate_masked` (interpolate with the background written as 0), `capture_step` (a whole step as a
 # HIP graph) and `set_depth_order` / `get_depth_order` (the rasterizer's depth order: the reference's source, or the
-# reference as its setup.py builds it) are this package's additions.  Not
+# reference as its setup.py builds it) are this package's additions.  The mesh geometry of drtk.utils (face_info,
+# vert_normals, face_attribute_to_vert, face_dpdt, vert_binormals) is exported here too.  Not
 # provided: grid_scatter, msi, filter2d and the pure-PyTorch `*_ref` models (out of scope).
 __all__ = [
     "rasterize",
@@ -39,4 +48,9 @@ __all__ = [
     "capture_step",
     "set_depth_order",
     "get_depth_order",
+    "face_info",
+    "vert_normals",
+    "face_attribute_to_vert",
+    "face_dpdt",
+    "vert_binormals",
 ]

@@ -147,6 +147,11 @@ EXPORTS = [
     "drtk_amd_screen_space_uv_derivative",
     "drtk_amd_transform_pinhole",
     "drtk_amd_transform_pinhole_backward",
+    "drtk_amd_geometry_face_forward",
+    "drtk_amd_geometry_face_backward",
+    "drtk_amd_geometry_face_gather",
+    "drtk_amd_geometry_vertex_gather_workspace_bytes",
+    "drtk_amd_geometry_vertex_gather",
     "drtk_amd_selftest_exact_div",
     "drtk_amd_kernel_timing_begin",
     "drtk_amd_kernel_timing_report",
@@ -530,6 +535,127 @@ def screen_space_uv_derivative(v, vt, vi, vti, index_img, bary_img, mask, campos
             _i(T), _i(vi_c.shape[0]), _i(H), _i(W), _p(out), _stream(bary_img, stream)),
         "screen_space_uv_derivative")
     return out
+
+
+GEOMETRY_CHUNK = 256  # DRTK_GEOMETRY_CHUNK of include/drtk_amd.h
+
+
+def vertex_incidence_numpy(vi, num_vertices: int, chunk: int = GEOMETRY_CHUNK):
+    """The vertex incidence the geometry entry points take (include/drtk_amd.h, "Mesh geometry"), built with numpy from
+    vi [F,3] or [B,F,3]: (crow [B*V+1], entries [3BF], chunk_ptr [B*V+1], chunk_begin [C], chunk_row [C]), int32."""
+    import numpy as np
+
+    t = np.asarray(vi, dtype=np.int64)
+    t = t[None] if t.ndim == 2 else t
+    B, F = t.shape[0], t.shape[1]
+    V = int(num_vertices)
+    keys = (t + (np.arange(B, dtype=np.int64) * V)[:, None, None]).reshape(-1)
+    perm = np.argsort(keys, kind="stable")
+    entries = (perm % max(3 * F, 1)).astype(np.int32)
+    crow = np.searchsorted(keys[perm], np.arange(B * V + 1), side="left").astype(np.int64)
+    length = np.diff(crow)
+    nch = np.where(length > chunk, (length + chunk - 1) // chunk, 0)
+    chunk_ptr = np.concatenate([[0], np.cumsum(nch)]).astype(np.int64)
+    chunk_row = np.repeat(np.arange(B * V), nch)
+    chunk_begin = crow[chunk_row] + (np.arange(len(chunk_row)) - chunk_ptr[chunk_row]) * chunk
+    return tuple(a.astype(np.int32) for a in (crow, entries, chunk_ptr, chunk_begin, chunk_row))
+
+
+def _geometry_topology(vi: th.Tensor):
+    """int32 vi [F,3] / [B,F,3] -> (contiguous tensor, batch stride in elements, B)"""
+    assert vi.dtype == th.int32
+    c = vi.contiguous()
+    if c.ndim == 2 or c.shape[0] == 1:
+        return c, 0, 1
+    return c, c.shape[1] * 3, c.shape[0]
+
+
+@_on_tensor_device
+def geometry_face_forward(v, vi, vt=None, vti=None, outputs=("normals", "areas", "edges"), stream=None):
+    """v [N,V,3], int32 vi [F,3] / [N,F,3]; with vt [N,T,2] and int32 vti [F,3] also "dpdt", "dpdt_u", "v012".
+    Returns {name: tensor} for the requested outputs."""
+    v = v.contiguous()
+    N, V = v.shape[0], v.shape[1]
+    vi_c, vi_sN, _ = _geometry_topology(vi)
+    F = vi_c.shape[-2]
+    shapes = {"normals": (N, F, 3), "areas": (N, F, 1), "edges": (N, F, 3, 3), "dpdt": (N, F, 2, 3),
+              "dpdt_u": (N, F, 3), "v012": (N, F, 3, 3)}
+    out = {k: _out(*shapes[k], dtype=v.dtype, device=v.device) for k in outputs}
+    vt_c = None if vt is None else vt.contiguous()
+    vti_c = None if vti is None else vti.contiguous()
+    T = 0 if vt_c is None else vt_c.shape[1]
+    _check(
+        lib().drtk_amd_geometry_face_forward(
+            ctypes.c_int(_dt(v)), _p(v), _i(V * 3), _p(vi_c), _i(vi_sN), _p(vt_c), _i(T * 2), _p(vti_c), _i(N), _i(V),
+            _i(T), _i(F), *(_p(out.get(k)) for k in ("normals", "areas", "edges", "dpdt", "dpdt_u", "v012")),
+            _stream(v, stream)),
+        "geometry_face_forward")
+    return out
+
+
+@_on_tensor_device
+def geometry_face_backward(v, vi, vt=None, vti=None, grad_vert=None, vert_sums=None, grad_normals=None,
+                           grad_areas=None, grad_edges=None, grad_dpdt=None, grad_v012=None, stream=None):
+    """Per-corner gradient rows of the face pass: positions [N,F,3,3] and (with vt) UVs [N,F,3,2] (None otherwise)."""
+    v = v.contiguous()
+    N, V = v.shape[0], v.shape[1]
+    vi_c, vi_sN, _ = _geometry_topology(vi)
+    F = vi_c.shape[-2]
+    vt_c = None if vt is None else vt.contiguous()
+    vti_c = None if vti is None else vti.contiguous()
+    T = 0 if vt_c is None else vt_c.shape[1]
+    pos = _out(N, F, 3, 3, dtype=v.dtype, device=v.device)
+    uv = None if vt_c is None else _out(N, F, 3, 2, dtype=v.dtype, device=v.device)
+    c = [None if g is None else g.contiguous() for g in (grad_vert, vert_sums, grad_normals, grad_areas, grad_edges,
+                                                          grad_dpdt, grad_v012)]
+    _check(
+        lib().drtk_amd_geometry_face_backward(
+            ctypes.c_int(_dt(v)), _p(v), _i(V * 3), _p(vi_c), _i(vi_sN), _p(vt_c), _i(T * 2), _p(vti_c), _i(N), _i(V),
+            _i(T), _i(F), *(_p(g) for g in c), _p(pos), _p(uv), _stream(v, stream)),
+        "geometry_face_backward")
+    return pos, uv
+
+
+@_on_tensor_device
+def geometry_face_gather(grad_vert, vi, num_faces=None, vert_sums=None, stream=None):
+    """[N,F,A] = sum over each face's corners of grad_vert [N,V,A] (through F.normalize's backward with vert_sums)."""
+    g = grad_vert.contiguous()
+    N, V, A = g.shape
+    vi_c, vi_sN, _ = _geometry_topology(vi)
+    F = vi_c.shape[-2]
+    out = _out(N, F, A, dtype=g.dtype, device=g.device)
+    s = None if vert_sums is None else vert_sums.contiguous()
+    _check(lib().drtk_amd_geometry_face_gather(ctypes.c_int(_dt(g)), _p(g), _p(s), _p(vi_c), _i(vi_sN), _i(N), _i(V),
+                                               _i(F), _i(A), _p(out), _stream(g, stream)),
+           "geometry_face_gather")
+    return out
+
+
+@_on_tensor_device
+def geometry_vertex_gather(src, incidence, num_vertices, per_corner=False, normalize=False, stream=None):
+    """src [N,F,A] (per_corner False) or [N,F,3,A]; incidence = vertex_incidence_numpy(...) as device tensors (or
+    numpy arrays, copied here).  Returns out [N,V,A] and, with normalize, the sums [N,V,3] (else None)."""
+    src = src.contiguous()
+    N, F, A = src.shape[0], src.shape[1], src.shape[-1]
+    inc = [th.as_tensor(a, dtype=th.int32, device=src.device).contiguous() for a in incidence]
+    crow, entries, chunk_ptr, chunk_begin, chunk_row = inc
+    V = int(num_vertices)
+    B = (crow.numel() - 1) // V if V else 1
+    C = chunk_row.numel()
+    out = _out(N, V, A, dtype=src.dtype, device=src.device)
+    sums = _out(N, V, 3, dtype=src.dtype, device=src.device) if normalize else None
+    need = ctypes.c_size_t(0)
+    _check(lib().drtk_amd_geometry_vertex_gather_workspace_bytes(ctypes.c_int(_dt(src)), _i(N), _i(B), _i(C), _i(A),
+                                                                 ctypes.byref(need)), "geometry_vertex_gather")
+    ws = _out(max(need.value, 1), dtype=th.uint8, device=src.device)
+    _check(
+        lib().drtk_amd_geometry_vertex_gather(
+            ctypes.c_int(_dt(src)), _p(src), _i(F * A * (3 if per_corner else 1)), ctypes.c_int(int(bool(per_corner))),
+            _i(A), _p(crow), _p(entries), _p(chunk_ptr if C else None), _p(chunk_begin if C else None),
+            _p(chunk_row if C else None), _i(C), _i(B), _i(N), _i(V), _i(F), ctypes.c_int(int(bool(normalize))), _p(out),
+            _p(sums), _p(ws), ctypes.c_size_t(need.value), _stream(src, stream)),
+        "geometry_vertex_gather")
+    return out, sums
 
 
 def edge_grad_backward_workspace_bytes(dtype, N, H, W) -> int:

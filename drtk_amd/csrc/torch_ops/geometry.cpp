@@ -1,0 +1,660 @@
+// drtk_amd_ext mesh-geometry operators -- drtk/utils/geometry.py of the reference (face_info, vert_normals,
+// face_attribute_to_vert, face_dpdt, vert_binormals) over drtk_amd_geometry_* (csrc/geometry.hip): a face pass and a
+// vertex pass that sums through the vertex incidence, each way, without float atomics.
+#include "common.hpp"
+
+#include <hip/hip_runtime_api.h>
+
+namespace {
+using namespace drtk_amd_torch;
+
+constexpr int64_t kChunk = DRTK_GEOMETRY_CHUNK;
+
+// ---------------------------------------------------------------------------------------------
+// Vertex incidence (CSR over rows b*V + vertex, entries f*3+k ascending within a row) and the chunk list of its long
+// rows, built where vi lives with ATen: stable sort of the keys b*V + vi[b,f,k] (the permutation is then ascending
+// within equal keys), searchsorted for the row starts.  One host read per build: the index range (an index outside
+// [0, V) would make the kernels read out of bounds) and the number of chunks (a launch size).
+// ---------------------------------------------------------------------------------------------
+struct Incidence {
+  Tensor vi32; // int32 [B,F,3] contiguous
+  Tensor crow, entries; // int32 [B*V+1], [3*B*F]
+  Tensor chunk_ptr, chunk_begin, chunk_row; // int32 [B*V+1], [C], [C]
+  int64_t B = 1, F = 0, V = 0, C = 0;
+};
+
+Incidence build_incidence(const Tensor& t, int64_t V, const char* op) {
+  Incidence inc;
+  inc.B = t.size(0), inc.F = t.size(1), inc.V = V;
+  TORCH_CHECK(V >= 0 && V < (int64_t(1) << 31), op, "(): expected the vertex count to fit in int32");
+  const int64_t R = inc.B * V, E = 3 * inc.B * inc.F;
+  TORCH_CHECK(E < (int64_t(1) << 31) && R < (int64_t(1) << 31), op, "(): mesh too large for int32 incidence");
+  const auto iopts = t.options().dtype(at::kInt);
+  const auto lopts = t.options().dtype(at::kLong);
+  const Tensor tl = t.detach().to(at::kLong).contiguous();
+  inc.vi32 = t.detach().to(at::kInt).contiguous();
+  inc.chunk_begin = at::empty({0}, iopts);
+  inc.chunk_row = at::empty({0}, iopts);
+  if (E == 0) {
+    inc.crow = at::zeros({R + 1}, iopts);
+    inc.entries = at::empty({0}, iopts);
+    inc.chunk_ptr = at::zeros({R + 1}, iopts);
+    return inc;
+  }
+  const Tensor keys = (tl + (at::arange(inc.B, lopts) * V).view({-1, 1, 1})).reshape({-1});
+  const auto sorted = at::sort(keys, /*stable=*/true, /*dim=*/0, /*descending=*/false);
+  inc.entries = at::remainder(std::get<1>(sorted), 3 * inc.F).to(at::kInt);
+  const Tensor crow = at::searchsorted(std::get<0>(sorted), at::arange(R + 1, lopts));
+  inc.crow = crow.to(at::kInt);
+  const Tensor len = crow.narrow(0, 1, R) - crow.narrow(0, 0, R);
+  const Tensor nch = at::where(len > kChunk, at::floor_divide(len + (kChunk - 1), kChunk), at::zeros_like(len));
+  const Tensor cptr = at::cat({at::zeros({1}, lopts), at::cumsum(nch, 0)});
+  const auto mm = at::aminmax(tl);
+  const Tensor stats = at::stack({std::get<0>(mm).reshape({}), std::get<1>(mm).reshape({}), cptr[R]}).cpu();
+  const int64_t* s = stats.data_ptr<int64_t>();
+  TORCH_CHECK(s[0] >= 0 && s[1] < V, op, "(): vi contains a vertex index outside [0, ", V, ")");
+  inc.C = s[2];
+  inc.chunk_ptr = cptr.to(at::kInt);
+  if (inc.C > 0) {
+    const Tensor rows = at::repeat_interleave(nch, std::optional<int64_t>(inc.C)); // row of each chunk
+    const Tensor j = at::arange(inc.C, lopts) - cptr.index_select(0, rows);
+    inc.chunk_row = rows.to(at::kInt);
+    inc.chunk_begin = (crow.index_select(0, rows) + j * kChunk).to(at::kInt);
+  }
+  return inc;
+}
+
+// Cache: NormalMatrixPatternCache's key and pinning rules (interp_matrix.cpp) -- identity + version of the index
+// tensor, no content hashing; an in-place edit bumps the version counter and misses; each entry pins its vi so that a
+// recycled allocation cannot alias a stale entry; 128 entries, LRU.
+struct TopologyKey {
+  std::array<int64_t, 14> f;
+  bool operator==(const TopologyKey& o) const {
+    return f == o.f;
+  }
+};
+struct TopologyKeyHash {
+  size_t operator()(const TopologyKey& k) const {
+    uint64_t h = 1469598103934665603ull; // FNV-1a over the fields
+    for (int64_t x : k.f) {
+      h ^= static_cast<uint64_t>(x);
+      h *= 1099511628211ull;
+    }
+    return static_cast<size_t>(h);
+  }
+};
+TopologyKey topology_key(const Tensor& vi, int64_t num_vertices) {
+  TopologyKey k;
+  k.f = {static_cast<int64_t>(vi.device().type()),
+         static_cast<int64_t>(vi.device().index()),
+         static_cast<int64_t>(reinterpret_cast<uintptr_t>(vi.storage().unsafeGetStorageImpl())),
+         static_cast<int64_t>(reinterpret_cast<uintptr_t>(vi.data_ptr())),
+         vi.size(0),
+         vi.size(1),
+         vi.size(2),
+         vi.stride(0),
+         vi.stride(1),
+         vi.stride(2),
+         vi.storage_offset(),
+         static_cast<int64_t>(vi.scalar_type()),
+         num_vertices,
+         static_cast<int64_t>(vi.unsafeGetTensorImpl()->version_counter().current_version())};
+  return k;
+}
+
+class IncidenceCache {
+ public:
+  static constexpr size_t kCapacity = 128;
+  static IncidenceCache& instance() {
+    static IncidenceCache c;
+    return c;
+  }
+  Incidence get(const Tensor& vi, int64_t num_vertices, const char* op) {
+    const TopologyKey key = topology_key(vi, num_vertices);
+    {
+      std::lock_guard<std::mutex> lock(mu_);
+      if (const Incidence* hit = touch(key)) {
+        ++hits_;
+        return *hit;
+      }
+    }
+    if (vi.is_cuda()) {
+      // the build reads two numbers back and allocates: not capturable
+      hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+      const hipStream_t s = c10::hip::getCurrentHIPStream(vi.device().index()).stream();
+      TORCH_CHECK(hipStreamIsCapturing(s, &st) != hipSuccess || st == hipStreamCaptureStatusNone, op,
+                  "(): the vertex incidence of this index tensor is not cached yet, and it cannot be built while the "
+                  "stream is being captured -- run the op once with the same vi before the capture");
+    }
+    Incidence built = build_incidence(vi, num_vertices, op);
+    std::lock_guard<std::mutex> lock(mu_);
+    if (const Incidence* hit = touch(key)) return *hit;
+    ++misses_;
+    while (lru_.size() >= kCapacity) {
+      index_.erase(lru_.back().key);
+      lru_.pop_back();
+    }
+    lru_.push_front(Entry{key, vi, built});
+    index_.emplace(key, lru_.begin());
+    return built;
+  }
+  std::vector<int64_t> stats() {
+    std::lock_guard<std::mutex> lock(mu_);
+    return {hits_, misses_, static_cast<int64_t>(lru_.size())};
+  }
+  void clear() {
+    std::lock_guard<std::mutex> lock(mu_);
+    lru_.clear();
+    index_.clear();
+    hits_ = misses_ = 0;
+  }
+
+ private:
+  struct Entry {
+    TopologyKey key;
+    Tensor pinned_vi;
+    Incidence inc;
+  };
+  const Incidence* touch(const TopologyKey& key) {
+    const auto it = index_.find(key);
+    if (it == index_.end()) return nullptr;
+    lru_.splice(lru_.begin(), lru_, it->second);
+    return &it->second->inc;
+  }
+  std::mutex mu_;
+  std::list<Entry> lru_;
+  std::unordered_map<TopologyKey, std::list<Entry>::iterator, TopologyKeyHash> index_;
+  int64_t hits_ = 0, misses_ = 0;
+};
+
+// vi [F,3] / [B,F,3] (B = 1 or N; a stride-0 expand counts as 1) -> its incidence over V vertices
+Incidence incidence_of(const Tensor& vi, int64_t N, int64_t V, const char* op) {
+  TORCH_CHECK(vi.defined() && vi.layout() == at::kStrided, op, "(): expected vi to be a strided tensor");
+  TORCH_CHECK(vi.scalar_type() == at::kInt || vi.scalar_type() == at::kLong, op,
+              "(): expected vi to be int32 or int64, got ", vi.scalar_type());
+  TORCH_CHECK((vi.dim() == 2 && vi.size(1) == 3) || (vi.dim() == 3 && vi.size(2) == 3), op,
+              "(): expected vi of shape [F,3] or [B,F,3]");
+  Tensor t = vi.dim() == 2 ? vi.unsqueeze(0) : vi;
+  if (t.size(0) > 1 && t.stride(0) == 0) t = t.narrow(0, 0, 1);
+  TORCH_CHECK(t.size(0) == 1 || t.size(0) == N, op, "(): expected the batch size of vi to be 1 or ", N, ", got ",
+              t.size(0));
+  return IncidenceCache::instance().get(t, V, op);
+}
+
+// Incidence tensors travel through autograd contexts as saved data
+void save_incidence(AutogradContext* ctx, const std::string& k, const Incidence& inc) {
+  ctx->saved_data[k + "vi"] = inc.vi32;
+  ctx->saved_data[k + "crow"] = inc.crow;
+  ctx->saved_data[k + "entries"] = inc.entries;
+  ctx->saved_data[k + "chunk_ptr"] = inc.chunk_ptr;
+  ctx->saved_data[k + "chunk_begin"] = inc.chunk_begin;
+  ctx->saved_data[k + "chunk_row"] = inc.chunk_row;
+  ctx->saved_data[k + "sizes"] = std::vector<int64_t>{inc.B, inc.F, inc.V, inc.C};
+}
+Incidence load_incidence(AutogradContext* ctx, const std::string& k) {
+  Incidence inc;
+  inc.vi32 = ctx->saved_data[k + "vi"].toTensor();
+  inc.crow = ctx->saved_data[k + "crow"].toTensor();
+  inc.entries = ctx->saved_data[k + "entries"].toTensor();
+  inc.chunk_ptr = ctx->saved_data[k + "chunk_ptr"].toTensor();
+  inc.chunk_begin = ctx->saved_data[k + "chunk_begin"].toTensor();
+  inc.chunk_row = ctx->saved_data[k + "chunk_row"].toTensor();
+  const auto s = ctx->saved_data[k + "sizes"].toIntVector();
+  inc.B = s[0], inc.F = s[1], inc.V = s[2], inc.C = s[3];
+  return inc;
+}
+
+int64_t vi_stride(const Incidence& inc) {
+  return inc.B == 1 ? 0 : inc.F * 3;
+}
+
+Tensor prep_v(const Tensor& v, const char* op) {
+  TORCH_CHECK(v.is_cuda(), op, "(): drtk_amd implements the MI355X (HIP) path only; got CPU tensors");
+  TORCH_CHECK(v.dim() == 3 && v.size(2) == 3, op, "(): expected v of shape [N, V, 3]");
+  dtype_of(v, op);
+  return v.contiguous();
+}
+Tensor like_v(const Tensor& t, const Tensor& v, const char* op, const char* what) {
+  TORCH_CHECK(t.device() == v.device(), op, "(): expected ", what, " on the device of v");
+  return t.to(v.scalar_type()).contiguous();
+}
+
+// out [N,V,A] (+ sums [N,V,3]) = per-vertex sums of src rows: [N,F,A] (per_corner false) or [N,F,3,A]
+Tensor vertex_gather(const Tensor& src, bool per_corner, int64_t A, const Incidence& inc, int64_t N, bool normalize,
+                     Tensor* sums, const char* op) {
+  const drtk_dtype_t dt = dtype_of(src, op);
+  auto out = out_empty({N, inc.V, A}, src.options());
+  Tensor s;
+  if (sums) s = out_empty({N, inc.V, 3}, src.options());
+  size_t bytes = 0;
+  check_status(drtk_amd_geometry_vertex_gather_workspace_bytes(dt, N, inc.B, inc.C, A, &bytes), op);
+  Tensor ws = bytes ? alloc_workspace(bytes, src) : Tensor();
+  const bool chunks = inc.C > 0;
+  check_status(
+      drtk_amd_geometry_vertex_gather(
+          dt, src.data_ptr(), inc.F * A * (per_corner ? 3 : 1), per_corner ? 1 : 0, A, inc.crow.data_ptr<int32_t>(),
+          inc.entries.data_ptr<int32_t>(), chunks ? inc.chunk_ptr.data_ptr<int32_t>() : nullptr,
+          chunks ? inc.chunk_begin.data_ptr<int32_t>() : nullptr, chunks ? inc.chunk_row.data_ptr<int32_t>() : nullptr,
+          inc.C, inc.B, N, inc.V, inc.F, normalize ? 1 : 0, out.data_ptr(), sums ? s.data_ptr() : nullptr,
+          ws.defined() ? ws.data_ptr() : nullptr, bytes, current_stream(src)),
+      op);
+  if (sums) *sums = s;
+  return out;
+}
+
+// grad [N,F,A] = sum over each face's corners of g [N,V,A] (through F.normalize's backward when sums is defined)
+Tensor face_gather(const Tensor& g, const Tensor& sums, const Incidence& inc, int64_t N, int64_t A, const char* op) {
+  auto out = out_empty({N, inc.F, A}, g.options());
+  check_status(drtk_amd_geometry_face_gather(
+                   dtype_of(g, op), g.data_ptr(), sums.defined() ? sums.data_ptr() : nullptr,
+                   inc.vi32.data_ptr<int32_t>(), vi_stride(inc), N, inc.V, inc.F, A, out.data_ptr(), current_stream(g)),
+               op);
+  return out;
+}
+
+const void* ptr_or_null(const Tensor& t) {
+  return t.defined() ? t.data_ptr() : nullptr;
+}
+
+// face pass forward; outputs that are not wanted are left undefined
+struct FaceOut {
+  Tensor normals, areas, edges, dpdt, dpdt_u, v012;
+};
+FaceOut face_forward(const Tensor& v, const Incidence& inc, const Tensor& vt, const Incidence* tinc, bool normals,
+                     bool areas, bool edges, bool dpdt, bool dpdt_u, bool v012, const char* op) {
+  const int64_t N = v.size(0), F = inc.F;
+  const auto o = v.options();
+  FaceOut r;
+  if (normals) r.normals = out_empty({N, F, 3}, o);
+  if (areas) r.areas = out_empty({N, F, 1}, o);
+  if (edges) r.edges = out_empty({N, F, 3, 3}, o);
+  if (dpdt) r.dpdt = out_empty({N, F, 2, 3}, o);
+  if (dpdt_u) r.dpdt_u = out_empty({N, F, 3}, o);
+  if (v012) r.v012 = out_empty({N, F, 3, 3}, o);
+  check_status(
+      drtk_amd_geometry_face_forward(
+          dtype_of(v, op), v.data_ptr(), v.size(1) * 3, inc.vi32.data_ptr<int32_t>(), vi_stride(inc),
+          tinc ? vt.data_ptr() : nullptr, tinc ? vt.size(1) * 2 : 0, tinc ? tinc->vi32.data_ptr<int32_t>() : nullptr,
+          N, v.size(1), tinc ? tinc->V : 0, F, normals ? r.normals.data_ptr() : nullptr,
+          areas ? r.areas.data_ptr() : nullptr, edges ? r.edges.data_ptr() : nullptr,
+          dpdt ? r.dpdt.data_ptr() : nullptr, dpdt_u ? r.dpdt_u.data_ptr() : nullptr,
+          v012 ? r.v012.data_ptr() : nullptr, current_stream(v)),
+      op);
+  return r;
+}
+
+// face pass backward -> grad_v [N,V,3] (and grad_vt [N,T,2] when tinc is given)
+// (only the reductions that are wanted: need_v / need_vt)
+std::pair<Tensor, Tensor> face_backward(const Tensor& v, const Incidence& inc, const Tensor& vt, const Incidence* tinc,
+                                        const Tensor& g_vert, const Tensor& sums, const Tensor& g_normals,
+                                        const Tensor& g_areas, const Tensor& g_edges, const Tensor& g_dpdt,
+                                        const Tensor& g_v012, bool need_v, bool need_vt, const char* op) {
+  const int64_t N = v.size(0), F = inc.F;
+  auto pos = out_empty({N, F, 3, 3}, v.options());
+  Tensor uv = tinc ? out_empty({N, F, 3, 2}, v.options()) : Tensor();
+  check_status(
+      drtk_amd_geometry_face_backward(
+          dtype_of(v, op), v.data_ptr(), v.size(1) * 3, inc.vi32.data_ptr<int32_t>(), vi_stride(inc),
+          tinc ? vt.data_ptr() : nullptr, tinc ? vt.size(1) * 2 : 0, tinc ? tinc->vi32.data_ptr<int32_t>() : nullptr,
+          N, v.size(1), tinc ? tinc->V : 0, F, ptr_or_null(g_vert), ptr_or_null(sums), ptr_or_null(g_normals),
+          ptr_or_null(g_areas), ptr_or_null(g_edges), ptr_or_null(g_dpdt), ptr_or_null(g_v012), pos.data_ptr(),
+          tinc ? uv.data_ptr() : nullptr, current_stream(v)),
+      op);
+  Tensor gv = need_v ? vertex_gather(pos, true, 3, inc, N, false, nullptr, op) : Tensor();
+  Tensor gvt = tinc && need_vt ? vertex_gather(uv, true, 2, *tinc, N, false, nullptr, op) : Tensor();
+  return {gv, gvt};
+}
+
+// Which inputs want a gradient is decided on the inputs as the caller passed them: the tensors the forward saves are the
+// contiguous copies the kernels read, and a copy made inside Function::forward (grad mode off) never requires grad --
+// an expanded, sliced or permuted v would silently get none.
+// (v: the differentiable input -- the attribute for face_attribute_to_vert and given fnorms)
+void save_requires_grad(AutogradContext* ctx, const Tensor& v, const Tensor& vt) {
+  ctx->saved_data["v_requires_grad"] = v.requires_grad();
+  ctx->saved_data["vt_requires_grad"] = vt.defined() && vt.requires_grad();
+}
+bool wants(AutogradContext* ctx, const char* k) {
+  return ctx->saved_data[k].toBool();
+}
+
+// The backward passes are kernels, not differentiable graphs: under create_graph=True their second-order terms would be
+// silently zero, so that is an error.
+void no_double_backward(const char* op) {
+  TORCH_CHECK(!at::GradMode::is_enabled(), op,
+              "(): double backward (create_graph=True) is not supported by drtk_amd's geometry kernels; the PyTorch "
+              "formulation (CPU tensors) supports it");
+}
+
+Tensor grad_or_undef(const Tensor& g, const Tensor& v) {
+  return g.defined() ? g.to(v.scalar_type()).contiguous() : Tensor();
+}
+
+// ---------------------------------------------------------------------------------------------
+// face_info
+// ---------------------------------------------------------------------------------------------
+using Tensor3 = std::tuple<Tensor, Tensor, Tensor>;
+
+Tensor3 face_info_hip(const Tensor& v_, const Tensor& vi, bool normals, bool areas, bool edges) {
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(v_.device());
+  const Tensor v = prep_v(v_, "face_info");
+  TORCH_CHECK(normals || areas || edges, "face_info(): nothing to compute");
+  const Incidence inc = incidence_of(vi, v.size(0), v.size(1), "face_info");
+  FaceOut r = face_forward(v, inc, Tensor(), nullptr, normals, areas, edges, false, false, false, "face_info");
+  const auto empty = at::empty({0}, v.options());
+  return {normals ? r.normals : empty, areas ? r.areas : empty, edges ? r.edges : empty};
+}
+
+class FaceInfoFunction : public torch::autograd::Function<FaceInfoFunction> {
+ public:
+  static tensor_list forward(AutogradContext* ctx, const Tensor& v_, const Tensor& vi, bool normals, bool areas,
+                             bool edges) {
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(v_.device());
+    ctx->set_materialize_grads(false);
+    const Tensor v = prep_v(v_, "face_info");
+    TORCH_CHECK(normals || areas || edges, "face_info(): nothing to compute");
+    const Incidence inc = incidence_of(vi, v.size(0), v.size(1), "face_info");
+    ctx->save_for_backward({v});
+    save_requires_grad(ctx, v_, Tensor());
+    save_incidence(ctx, "", inc);
+    at::AutoDispatchBelowADInplaceOrView g;
+    FaceOut r = face_forward(v, inc, Tensor(), nullptr, normals, areas, edges, false, false, false, "face_info");
+    const auto empty = at::empty({0}, v.options());
+    return {normals ? r.normals : empty, areas ? r.areas : empty, edges ? r.edges : empty};
+  }
+  static tensor_list backward(AutogradContext* ctx, tensor_list go) {
+    const Tensor v = ctx->get_saved_variables()[0];
+    const Tensor gn = go[0].defined() && go[0].numel() ? grad_or_undef(go[0], v) : Tensor();
+    const Tensor ga = go[1].defined() && go[1].numel() ? grad_or_undef(go[1], v) : Tensor();
+    const Tensor ge = go[2].defined() && go[2].numel() ? grad_or_undef(go[2], v) : Tensor();
+    if (!(gn.defined() || ga.defined() || ge.defined()) || !wants(ctx, "v_requires_grad"))
+      return {Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+    no_double_backward("face_info_backward");
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(v.device());
+    const Incidence inc = load_incidence(ctx, "");
+    auto gvs = face_backward(v, inc, Tensor(), nullptr, Tensor(), Tensor(), gn, ga, ge, Tensor(), Tensor(), true, false,
+                             "face_info_backward");
+    return {gvs.first, Tensor(), Tensor(), Tensor(), Tensor()};
+  }
+};
+Tensor3 face_info_autograd(const Tensor& v, const Tensor& vi, bool normals, bool areas, bool edges) {
+  auto r = FaceInfoFunction::apply(v, vi, normals, areas, edges);
+  return {r[0], r[1], r[2]};
+}
+
+// ---------------------------------------------------------------------------------------------
+// vert_normals (face normals from v, or given as fnorms) and face_attribute_to_vert
+// ---------------------------------------------------------------------------------------------
+Tensor vert_normals_hip(const Tensor& v_, const Tensor& vi, const c10::optional<Tensor>& fnorms) {
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(v_.device());
+  const Tensor v = prep_v(v_, "vert_normals");
+  const int64_t N = v.size(0);
+  const Incidence inc = incidence_of(vi, N, v.size(1), "vert_normals");
+  Tensor fn;
+  if (fnorms.has_value() && fnorms->defined()) {
+    fn = like_v(*fnorms, v, "vert_normals", "fnorms");
+    TORCH_CHECK(fn.dim() == 3 && fn.size(0) == N && fn.size(1) == inc.F && fn.size(2) == 3,
+                "vert_normals(): expected fnorms of shape [N, F, 3]");
+  } else {
+    fn = face_forward(v, inc, Tensor(), nullptr, true, false, false, false, false, false, "vert_normals").normals;
+  }
+  return vertex_gather(fn, false, 3, inc, N, true, nullptr, "vert_normals");
+}
+
+class VertNormalsFunction : public torch::autograd::Function<VertNormalsFunction> {
+ public:
+  static tensor_list forward(AutogradContext* ctx, const Tensor& v_, const Tensor& vi) {
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(v_.device());
+    ctx->set_materialize_grads(false);
+    const Tensor v = prep_v(v_, "vert_normals");
+    const Incidence inc = incidence_of(vi, v.size(0), v.size(1), "vert_normals");
+    at::AutoDispatchBelowADInplaceOrView g;
+    const Tensor fn = face_forward(v, inc, Tensor(), nullptr, true, false, false, false, false, false, "vert_normals").normals;
+    Tensor sums;
+    Tensor out = vertex_gather(fn, false, 3, inc, v.size(0), true, &sums, "vert_normals");
+    ctx->save_for_backward({v, sums});
+    save_requires_grad(ctx, v_, Tensor());
+    save_incidence(ctx, "", inc);
+    return {out};
+  }
+  static tensor_list backward(AutogradContext* ctx, tensor_list go) {
+    const auto saved = ctx->get_saved_variables();
+    const Tensor& v = saved[0];
+    if (!go[0].defined() || !wants(ctx, "v_requires_grad")) return {Tensor(), Tensor()};
+    no_double_backward("vert_normals_backward");
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(v.device());
+    const Incidence inc = load_incidence(ctx, "");
+    auto gvs = face_backward(v, inc, Tensor(), nullptr, grad_or_undef(go[0], v), saved[1], Tensor(), Tensor(), Tensor(),
+                             Tensor(), Tensor(), true, false, "vert_normals_backward");
+    return {gvs.first, Tensor()};
+  }
+};
+
+// vert_normals with given face normals, and face_attribute_to_vert: per-vertex sums of a per-face attribute, normalised
+// or not; the gradient goes to the attribute only.
+class FaceToVertFunction : public torch::autograd::Function<FaceToVertFunction> {
+ public:
+  static tensor_list forward(AutogradContext* ctx, const Tensor& attr_, const Tensor& v_, const Tensor& vi,
+                             bool normalize) {
+    const char* op = normalize ? "vert_normals" : "face_attribute_to_vert";
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(v_.device());
+    ctx->set_materialize_grads(false);
+    TORCH_CHECK(v_.is_cuda(), op, "(): drtk_amd implements the MI355X (HIP) path only; got CPU tensors");
+    TORCH_CHECK(v_.dim() >= 2, op, "(): expected v of shape [N, V, *]");
+    dtype_of(v_, op);
+    const int64_t N = v_.size(0);
+    const Incidence inc = incidence_of(vi, N, v_.size(1), op);
+    const Tensor attr = like_v(attr_, v_, op, normalize ? "fnorms" : "attr");
+    TORCH_CHECK(attr.dim() == 3 && attr.size(0) == N && attr.size(1) == inc.F && (!normalize || attr.size(2) == 3), op,
+                "(): expected ", normalize ? "fnorms of shape [N, F, 3]" : "attr of shape [N, F, A]");
+    TORCH_CHECK(attr.size(2) >= 1, op, "(): expected at least one attribute channel");
+    at::AutoDispatchBelowADInplaceOrView g;
+    Tensor sums;
+    Tensor out = vertex_gather(attr, false, attr.size(2), inc, N, normalize, normalize ? &sums : nullptr, op);
+    ctx->save_for_backward({sums});
+    save_requires_grad(ctx, attr_, Tensor());
+    save_incidence(ctx, "", inc);
+    ctx->saved_data["A"] = attr.size(2);
+    ctx->saved_data["attr_dtype"] = static_cast<int64_t>(attr_.scalar_type());
+    return {out};
+  }
+  static tensor_list backward(AutogradContext* ctx, tensor_list go) {
+    const auto saved = ctx->get_saved_variables();
+    if (!go[0].defined() || !wants(ctx, "v_requires_grad")) return {Tensor(), Tensor(), Tensor(), Tensor()};
+    no_double_backward("face_attribute_to_vert_backward");
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(go[0].device());
+    const Incidence inc = load_incidence(ctx, "");
+    const int64_t A = ctx->saved_data["A"].toInt();
+    const Tensor g = go[0].contiguous(); // dtype of v, in which the forward ran
+    Tensor ga = face_gather(g, saved[0], inc, g.size(0), A, "face_attribute_to_vert_backward");
+    return {ga.to(static_cast<at::ScalarType>(ctx->saved_data["attr_dtype"].toInt())), Tensor(), Tensor(), Tensor()};
+  }
+};
+
+Tensor vert_normals_autograd(const Tensor& v, const Tensor& vi, const c10::optional<Tensor>& fnorms) {
+  if (fnorms.has_value() && fnorms->defined()) return FaceToVertFunction::apply(*fnorms, v, vi, true)[0];
+  return VertNormalsFunction::apply(v, vi)[0];
+}
+
+Tensor face_attribute_to_vert_hip(const Tensor& v, const Tensor& vi, const Tensor& attr_) {
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(v.device());
+  TORCH_CHECK(v.is_cuda(), "face_attribute_to_vert(): drtk_amd implements the MI355X (HIP) path only; got CPU tensors");
+  TORCH_CHECK(v.dim() >= 2, "face_attribute_to_vert(): expected v of shape [N, V, *]");
+  dtype_of(v, "face_attribute_to_vert");
+  const int64_t N = v.size(0);
+  const Incidence inc = incidence_of(vi, N, v.size(1), "face_attribute_to_vert");
+  const Tensor attr = like_v(attr_, v, "face_attribute_to_vert", "attr");
+  TORCH_CHECK(attr.dim() == 3 && attr.size(0) == N && attr.size(1) == inc.F && attr.size(2) >= 1,
+              "face_attribute_to_vert(): expected attr of shape [N, F, A]");
+  return vertex_gather(attr, false, attr.size(2), inc, N, false, nullptr, "face_attribute_to_vert");
+}
+Tensor face_attribute_to_vert_autograd(const Tensor& v, const Tensor& vi, const Tensor& attr) {
+  return FaceToVertFunction::apply(attr, v, vi, false)[0];
+}
+
+// ---------------------------------------------------------------------------------------------
+// face_dpdt and vert_binormals (vi, vti: [F,3])
+// ---------------------------------------------------------------------------------------------
+struct DpdtArgs {
+  Tensor v, vt;
+  Incidence inc, tinc;
+};
+DpdtArgs dpdt_prep(const Tensor& v_, const Tensor& vt_, const Tensor& vi, const Tensor& vti, const char* op) {
+  DpdtArgs a;
+  a.v = prep_v(v_, op);
+  TORCH_CHECK(vt_.dim() == 3 && vt_.size(2) == 2, op, "(): expected vt of shape [N, T, 2]");
+  TORCH_CHECK(vt_.size(0) == a.v.size(0), op, "(): expected vt to have the same batch size as v, got ", vt_.size(0),
+              " and ", a.v.size(0));
+  a.vt = like_v(vt_, a.v, op, "vt");
+  TORCH_CHECK(vi.dim() == 2 && vti.dim() == 2, op, "(): expected vi and vti of shape [F, 3]");
+  TORCH_CHECK(vi.size(0) == vti.size(0), op, "(): expected vi and vti to list the same faces");
+  a.inc = incidence_of(vi, a.v.size(0), a.v.size(1), op);
+  a.tinc = incidence_of(vti, a.v.size(0), a.vt.size(1), op);
+  return a;
+}
+
+std::tuple<Tensor, Tensor> face_dpdt_hip(const Tensor& v, const Tensor& vt, const Tensor& vi, const Tensor& vti) {
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(v.device());
+  const DpdtArgs a = dpdt_prep(v, vt, vi, vti, "face_dpdt");
+  FaceOut r = face_forward(a.v, a.inc, a.vt, &a.tinc, false, false, false, true, false, true, "face_dpdt");
+  return {r.dpdt, r.v012};
+}
+
+class FaceDpdtFunction : public torch::autograd::Function<FaceDpdtFunction> {
+ public:
+  static tensor_list forward(AutogradContext* ctx, const Tensor& v, const Tensor& vt, const Tensor& vi,
+                             const Tensor& vti) {
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(v.device());
+    ctx->set_materialize_grads(false);
+    const DpdtArgs a = dpdt_prep(v, vt, vi, vti, "face_dpdt");
+    ctx->save_for_backward({a.v, a.vt});
+    save_requires_grad(ctx, v, vt);
+    save_incidence(ctx, "p", a.inc);
+    save_incidence(ctx, "t", a.tinc);
+    at::AutoDispatchBelowADInplaceOrView g;
+    FaceOut r = face_forward(a.v, a.inc, a.vt, &a.tinc, false, false, false, true, false, true, "face_dpdt");
+    return {r.dpdt, r.v012};
+  }
+  static tensor_list backward(AutogradContext* ctx, tensor_list go) {
+    const auto saved = ctx->get_saved_variables();
+    const Tensor &v = saved[0], &vt = saved[1];
+    const bool need_v = wants(ctx, "v_requires_grad"), need_vt = wants(ctx, "vt_requires_grad");
+    if (!(go[0].defined() || go[1].defined()) || !(need_v || need_vt)) return {Tensor(), Tensor(), Tensor(), Tensor()};
+    no_double_backward("face_dpdt_backward");
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(v.device());
+    const Incidence inc = load_incidence(ctx, "p"), tinc = load_incidence(ctx, "t");
+    auto g = face_backward(v, inc, vt, &tinc, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), grad_or_undef(go[0], v),
+                           grad_or_undef(go[1], v), need_v, need_vt, "face_dpdt_backward");
+    return {g.first, g.second, Tensor(), Tensor()};
+  }
+};
+std::tuple<Tensor, Tensor> face_dpdt_autograd(const Tensor& v, const Tensor& vt, const Tensor& vi, const Tensor& vti) {
+  auto r = FaceDpdtFunction::apply(v, vt, vi, vti);
+  return {r[0], r[1]};
+}
+
+Tensor vert_binormals_hip(const Tensor& v, const Tensor& vt, const Tensor& vi, const Tensor& vti) {
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(v.device());
+  const DpdtArgs a = dpdt_prep(v, vt, vi, vti, "vert_binormals");
+  const Tensor u = face_forward(a.v, a.inc, a.vt, &a.tinc, false, false, false, false, true, false, "vert_binormals").dpdt_u;
+  return vertex_gather(u, false, 3, a.inc, a.v.size(0), true, nullptr, "vert_binormals");
+}
+
+class VertBinormalsFunction : public torch::autograd::Function<VertBinormalsFunction> {
+ public:
+  static tensor_list forward(AutogradContext* ctx, const Tensor& v, const Tensor& vt, const Tensor& vi,
+                             const Tensor& vti) {
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(v.device());
+    ctx->set_materialize_grads(false);
+    const DpdtArgs a = dpdt_prep(v, vt, vi, vti, "vert_binormals");
+    at::AutoDispatchBelowADInplaceOrView g;
+    const Tensor u =
+        face_forward(a.v, a.inc, a.vt, &a.tinc, false, false, false, false, true, false, "vert_binormals").dpdt_u;
+    Tensor sums;
+    Tensor out = vertex_gather(u, false, 3, a.inc, a.v.size(0), true, &sums, "vert_binormals");
+    ctx->save_for_backward({a.v, a.vt, sums});
+    save_requires_grad(ctx, v, vt);
+    save_incidence(ctx, "p", a.inc);
+    save_incidence(ctx, "t", a.tinc);
+    return {out};
+  }
+  static tensor_list backward(AutogradContext* ctx, tensor_list go) {
+    const auto saved = ctx->get_saved_variables();
+    const Tensor &v = saved[0], &vt = saved[1];
+    const bool need_v = wants(ctx, "v_requires_grad"), need_vt = wants(ctx, "vt_requires_grad");
+    if (!go[0].defined() || !(need_v || need_vt)) return {Tensor(), Tensor(), Tensor(), Tensor()};
+    no_double_backward("vert_binormals_backward");
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(v.device());
+    const Incidence inc = load_incidence(ctx, "p"), tinc = load_incidence(ctx, "t");
+    auto g = face_backward(v, inc, vt, &tinc, grad_or_undef(go[0], v), saved[2], Tensor(), Tensor(), Tensor(), Tensor(),
+                           Tensor(), need_v, need_vt, "vert_binormals_backward");
+    return {g.first, g.second, Tensor(), Tensor()};
+  }
+};
+Tensor vert_binormals_autograd(const Tensor& v, const Tensor& vt, const Tensor& vi, const Tensor& vti) {
+  return VertBinormalsFunction::apply(v, vt, vi, vti)[0];
+}
+
+// ---------------------------------------------------------------------------------------------
+// incidence and cache (extension)
+// ---------------------------------------------------------------------------------------------
+std::tuple<Tensor, Tensor> vertex_incidence(const Tensor& vi, int64_t num_vertices) {
+  TORCH_CHECK(vi.dim() == 2 || vi.dim() == 3, "vertex_incidence(): expected vi of shape [F,3] or [B,F,3]");
+  const Incidence inc = incidence_of(vi, vi.dim() == 3 ? vi.size(0) : 1, num_vertices, "vertex_incidence");
+  return {inc.crow, inc.entries};
+}
+std::vector<int64_t> geometry_cache_stats() {
+  return IncidenceCache::instance().stats();
+}
+void geometry_cache_clear() {
+  IncidenceCache::instance().clear();
+}
+
+Tensor3 face_info_cpu(const Tensor&, const Tensor&, bool, bool, bool) {
+  no_cpu("face_info");
+}
+Tensor vert_normals_cpu(const Tensor&, const Tensor&, const c10::optional<Tensor>&) {
+  no_cpu("vert_normals");
+}
+Tensor face_attribute_to_vert_cpu(const Tensor&, const Tensor&, const Tensor&) {
+  no_cpu("face_attribute_to_vert");
+}
+std::tuple<Tensor, Tensor> face_dpdt_cpu(const Tensor&, const Tensor&, const Tensor&, const Tensor&) {
+  no_cpu("face_dpdt");
+}
+Tensor vert_binormals_cpu(const Tensor&, const Tensor&, const Tensor&, const Tensor&) {
+  no_cpu("vert_binormals");
+}
+
+} // namespace
+
+TORCH_LIBRARY_FRAGMENT(drtk_amd_ext, m) {
+  m.def("face_info(Tensor v, Tensor vi, bool normals, bool areas, bool edges) -> (Tensor, Tensor, Tensor)");
+  m.def("vert_normals(Tensor v, Tensor vi, Tensor? fnorms=None) -> Tensor");
+  m.def("face_attribute_to_vert(Tensor v, Tensor vi, Tensor attr) -> Tensor");
+  m.def("face_dpdt(Tensor v, Tensor vt, Tensor vi, Tensor vti) -> (Tensor, Tensor)");
+  m.def("vert_binormals(Tensor v, Tensor vt, Tensor vi, Tensor vti) -> Tensor");
+  m.def("vertex_incidence(Tensor vi, int num_vertices) -> (Tensor, Tensor)", &vertex_incidence);
+  m.def("geometry_cache_stats() -> int[]", &geometry_cache_stats);
+  m.def("geometry_cache_clear() -> ()", &geometry_cache_clear);
+}
+TORCH_LIBRARY_IMPL(drtk_amd_ext, Autograd, m) {
+  m.impl("face_info", &face_info_autograd);
+  m.impl("vert_normals", &vert_normals_autograd);
+  m.impl("face_attribute_to_vert", &face_attribute_to_vert_autograd);
+  m.impl("face_dpdt", &face_dpdt_autograd);
+  m.impl("vert_binormals", &vert_binormals_autograd);
+}
+TORCH_LIBRARY_IMPL(drtk_amd_ext, CUDA, m) {
+  m.impl("face_info", &face_info_hip);
+  m.impl("vert_normals", &vert_normals_hip);
+  m.impl("face_attribute_to_vert", &face_attribute_to_vert_hip);
+  m.impl("face_dpdt", &face_dpdt_hip);
+  m.impl("vert_binormals", &vert_binormals_hip);
+}
+TORCH_LIBRARY_IMPL(drtk_amd_ext, CPU, m) {
+  m.impl("face_info", &face_info_cpu);
+  m.impl("vert_normals", &vert_normals_cpu);
+  m.impl("face_attribute_to_vert", &face_attribute_to_vert_cpu);
+  m.impl("face_dpdt", &face_dpdt_cpu);
+  m.impl("vert_binormals", &vert_binormals_cpu);
+}

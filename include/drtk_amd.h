@@ -324,6 +324,67 @@ int drtk_amd_transform_pinhole_backward(
     const void* focal, const void* princpt, const void* grad_v_pix, int64_t N, int64_t V,
     void* grad_v, drtk_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mesh geometry -- drtk.utils.geometry (face_info, vert_normals, face_attribute_to_vert, face_dpdt, vert_binormals;
+ * pure PyTorch in the reference: drtk/utils/geometry.py) in two passes without float atomics.
+ *
+ * Shapes: v [N,V,3] (v_sN = 3V, or 0: one [V,3] shared by the views); vi int32 [N,F,3] (vi_sN = 3F) or [F,3]
+ * (vi_sN = 0); vt [N,T,2] (vt_sN = 2T or 0); vti int32 [F,3].  Every launch is a 1-D grid over N*F or N*V lanes with
+ * 64-bit offsets (any N).
+ *
+ * Vertex incidence (CSR), built by the caller once per index tensor (drtk_amd_ext::vertex_incidence builds and caches
+ * it; drtk_amd/capi.py has a numpy builder):
+ *   B        topology batches: 1 (vi shared by all views) or N
+ *   crow     int32 [B*V+1]   row r = b*V + vertex; crow[0] = 0, crow[B*V] = 3*B*F
+ *   entries  int32 [3*B*F]   the (face, corner) pairs f*3+k of row r, local to its batch, ASCENDING within the row
+ * Rows longer than DRTK_GEOMETRY_CHUNK entries are summed in chunks of that length (an empty chunk list is allowed
+ * when no row is longer):
+ *   chunk_ptr   int32 [B*V+1]  row r's chunks are chunk_ptr[r] .. chunk_ptr[r+1]-1 (none: the row is short)
+ *   chunk_begin int32 [C]      first entry of the chunk (crow[row] + j*DRTK_GEOMETRY_CHUNK for its j-th chunk)
+ *   chunk_row   int32 [C]      its row
+ * The kernels trust the incidence (it is not validated on the device): every crow / entries / chunk value must lie in
+ * range, and every index of vi / vti in [0, V) / [0, T).
+ *
+ * face_forward: per (view, face) with c = (p0 - p2) x (p1 - p0): normals [N,F,3] = c / max(|c|, 1e-8),
+ *   areas [N,F,1] = |c| / 2, edges [N,F,3,3] = (p1-p0, p0-p2, p2-p1), and with vt/vti: dpdt [N,F,2,3] =
+ *   inv([t1-t0; t2-t0]) [p1-p0; p2-p0] (closed-form 2x2 inverse: a singular UV matrix gives inf / nan where the
+ *   reference raises), dpdt_u [N,F,3] = its first row, v012 [N,F,3,3] = (p0, p1, p2).  NULL outputs are skipped;
+ *   at least one must be given.
+ * face_backward: per-corner gradient rows pos_rows [N,F,3,3] (and, with vt given, uv_rows [N,F,3,2]) of the face
+ *   pass from the optional upstream gradients grad_normals / grad_areas / grad_edges (vt NULL) or grad_dpdt /
+ *   grad_v012 (vt given), plus an optional per-VERTEX gradient grad_vert [N,V,3] gathered at the three corners -- of
+ *   the normals (vt NULL: vert_normals) or of dpdt's first row (vt given: vert_binormals) -- through F.normalize's
+ *   backward (eps 1e-12) from vert_sums [N,V,3], the unnormalised sums, when those are given.  Reduce the rows to
+ *   grad_v (grad_vt) with vertex_gather (per_corner = 1) over the vi (vti) incidence.
+ * face_gather: out [N,F,A] = sum over the three corners of grad_vert [N,V,A] (through F.normalize's backward from
+ *   vert_sums when given; A = 3 then): the backward of face_attribute_to_vert.
+ * vertex_gather: out [N,V,A] = per row, the sum of src rows (src [N,F,A] with per_corner = 0: row f = entry / 3;
+ *   [N,F,3,A] with per_corner = 1: row = entry; src_sN = F*A*(per_corner ? 3 : 1)) in entry order; a chunked row adds
+ *   its chunk sums in chunk order.  normalize = 1 (A = 3): out = sum / max(|sum|, 1e-12) and vert_sums (optional)
+ *   receives the sums.  With chunks the call needs a workspace of _workspace_bytes (any alignment of the element type).
+ * Results are bitwise reproducible: every sum has one fixed order, independent of the launch shape.
+ */
+#define DRTK_GEOMETRY_CHUNK 256
+int drtk_amd_geometry_face_forward(
+    drtk_dtype_t dtype, const void* v, int64_t v_sN, const int32_t* vi, int64_t vi_sN, const void* vt, int64_t vt_sN,
+    const int32_t* vti, int64_t N, int64_t V, int64_t T, int64_t F, void* normals, void* areas, void* edges,
+    void* dpdt, void* dpdt_u, void* v012, drtk_stream_t stream);
+int drtk_amd_geometry_face_backward(
+    drtk_dtype_t dtype, const void* v, int64_t v_sN, const int32_t* vi, int64_t vi_sN, const void* vt, int64_t vt_sN,
+    const int32_t* vti, int64_t N, int64_t V, int64_t T, int64_t F, const void* grad_vert, const void* vert_sums,
+    const void* grad_normals, const void* grad_areas, const void* grad_edges, const void* grad_dpdt,
+    const void* grad_v012, void* pos_rows, void* uv_rows, drtk_stream_t stream);
+int drtk_amd_geometry_face_gather(
+    drtk_dtype_t dtype, const void* grad_vert, const void* vert_sums, const int32_t* vi, int64_t vi_sN, int64_t N,
+    int64_t V, int64_t F, int64_t A, void* out, drtk_stream_t stream);
+int drtk_amd_geometry_vertex_gather_workspace_bytes(
+    drtk_dtype_t dtype, int64_t N, int64_t B, int64_t num_chunks, int64_t A, size_t* bytes);
+int drtk_amd_geometry_vertex_gather(
+    drtk_dtype_t dtype, const void* src, int64_t src_sN, int per_corner, int64_t A, const int32_t* crow,
+    const int32_t* entries, const int32_t* chunk_ptr, const int32_t* chunk_begin, const int32_t* chunk_row,
+    int64_t num_chunks, int64_t B, int64_t N, int64_t V, int64_t F, int normalize, void* out, void* vert_sums,
+    void* workspace, size_t workspace_bytes, drtk_stream_t stream);
+
 /* Diagnostics: compares the rasterizer's reciprocal-based exact division with the IEEE `/` on `count`
  * pseudo-random operand pairs on the device; *d_mismatches (device memory) receives the number of
  * differing results (must be 0). */
