@@ -19,7 +19,14 @@ from drtk_amd.interpolate import (  # noqa: F401
     interpolation_normal_matrix,
 )
 from drtk_amd.mipmap_grid_sample import mipmap_grid_sample  # noqa: F401
-from drtk_amd.rasterize import get_depth_order, rasterize, rasterize_with_depth, set_depth_order  # noqa: F401
+from drtk_amd.rasterize import (  # noqa: F401
+    get_depth_order,
+    rasterize,
+    rasterize_layers,
+    rasterize_layers_with_depth,
+    rasterize_with_depth,
+    set_depth_order,
+)
 from drtk_amd.render import render  # noqa: F401
 from drtk_amd.screen_space_uv_derivative import screen_space_uv_derivative  # noqa: F401
 from drtk_amd.transform import transform, transform_with_v_cam  # noqa: F401
@@ -29,12 +36,15 @@ __version__ = "0.1.0"
 # The public surface.  Same names, arguments and defaults as `drtk.*` for everything on the hot path and its "next"
 # rows; `interpolate_masked` (interpolate with the background written as 0), `capture_step` (a whole step as a
 # HIP graph) and `set_depth_order` / `get_depth_order` (the rasterizer's depth order: the reference's source, or the
-# reference as its setup.py builds it) are this package's additions.  The mesh geometry of drtk.utils (face_info,
+# reference as its setup.py builds it) and `rasterize_layers` / `rasterize_layers_with_depth` (the K nearest triangles per
+# pixel, for front-to-back compositing) are this package's additions.  The mesh geometry of drtk.utils (face_info,
 # vert_normals, face_attribute_to_vert, face_dpdt, vert_binormals) is exported here too.  Not
 # provided: grid_scatter, msi, filter2d and the pure-PyTorch `*_ref` models (out of scope).
 __all__ = [
     "rasterize",
     "rasterize_with_depth",
+    "rasterize_layers",
+    "rasterize_layers_with_depth",
     "render",
     "interpolate",
     "interpolate_masked",

@@ -127,6 +127,8 @@ EXPORTS = [
     "drtk_amd_rasterize_workspace_bytes",
     "drtk_amd_rasterize_lines_workspace_bytes",
     "drtk_amd_rasterize",
+    "drtk_amd_rasterize_layers_workspace_bytes",
+    "drtk_amd_rasterize_layers",
     "drtk_amd_render",
     "drtk_amd_render_backward",
     "drtk_amd_interpolate",
@@ -266,6 +268,42 @@ def rasterize(v, vi, height, width, stream=None, workspace=None, wireframe=False
             ctypes.c_int(1 if wireframe else 0), _p(depth), _p(index), _p(ws), ctypes.c_size_t(ws.numel()),
             _stream(v, stream)),
         "rasterize")
+    return depth, index
+
+
+MAX_RASTER_LAYERS = 8  # DRTK_AMD_MAX_RASTER_LAYERS (include/drtk_amd.h)
+
+
+def rasterize_layers_workspace_bytes(N, F, H, W, num_layers) -> int:
+    out = ctypes.c_size_t(0)
+    _check(
+        lib().drtk_amd_rasterize_layers_workspace_bytes(_i(N), _i(F), _i(H), _i(W), ctypes.c_int(int(num_layers)), ctypes.byref(out)),
+        "rasterize_layers")
+    return out.value
+
+
+@_on_tensor_device
+def rasterize_layers(v, vi, height, width, num_layers, stream=None, workspace=None, out=None) -> Tuple[th.Tensor, th.Tensor]:
+    """The `num_layers` nearest triangles per pixel: (depth_img, index_img), [N,K,H,W] float32 / int32.
+    `out` = (depth_img, index_img) to write into (contiguous, any element offset of a larger buffer)."""
+    v = v.contiguous()
+    N, V, _ = v.shape
+    K = int(num_layers)
+    vi_c, vi_sN, F = _vi(vi, N)
+    nbytes = rasterize_layers_workspace_bytes(N, F, height, width, K)  # raises on a bad num_layers, before any allocation
+    if out is not None:
+        depth, index = out
+        assert depth.shape == (N, K, height, width) and index.shape == (N, K, height, width) and depth.is_contiguous() and index.is_contiguous()
+        assert depth.dtype == th.float32 and index.dtype == th.int32
+    else:
+        depth = _out(N, K, height, width, dtype=th.float32, device=v.device)
+        index = _out(N, K, height, width, dtype=th.int32, device=v.device)
+    ws = workspace if workspace is not None else _out(nbytes, dtype=th.uint8, device=v.device)
+    _check(
+        lib().drtk_amd_rasterize_layers(
+            ctypes.c_int(_dt(v)), _p(v), _p(vi_c), _i(N), _i(V), _i(F), _i(vi_sN), _i(height), _i(width),
+            ctypes.c_int(K), _p(depth), _p(index), _p(ws), ctypes.c_size_t(ws.numel()), _stream(v, stream)),
+        "rasterize_layers")
     return depth, index
 
 

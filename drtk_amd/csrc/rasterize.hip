@@ -24,6 +24,10 @@
 // memset, no global atomics, no unpack pass (the reference moves >= 24 B/px).
 // The min-reduction over (depth bits, id) is order independent, so the result is deterministic
 // and bit-identical to the reference regardless of bin order.
+//
+// rasterize_layers (the K nearest triangles per pixel; no counterpart in the reference) reuses passes 1-3 once per call
+// and launches pass 4 once per layer: layer k >= 1 is "the smallest key strictly greater than layer k - 1's key at this
+// pixel", a compile-time variant of the same kernel body (kLayerPeel) with the previous layer's keys in a second LDS tile.
 #include <algorithm>
 
 #include "common.hpp"
@@ -200,6 +204,24 @@ __device__ __forceinline__ uint32_t z_lower_bound_bits(T min_x, T max_x, T min_y
   const float lo = static_cast<float>(zb < cap ? zb : cap);
   const uint32_t bits = __float_as_uint(lo);
   return (lo > 0.0f && bits > 8u) ? bits - 8u : 0u; // 8 ulps below, against the rounding of `lo` itself
+}
+
+// The mirror image, for the peeled layers of rasterize_layers: sum b_k >= 1 - 40 eps L^2 / |den| by the same error budget,
+// so depth <= (1 / min_k dinv_k) / (1 - delta) with dinv_k = 1 / z_k as the set-up rounds them (epsclamp of the sum only
+// ever lowers a depth).  Returns the f32 bits of a rigorous upper bound of every depth the triangle can produce,
+// 0xFFFFFFFF if there is none.
+template <typename T>
+__device__ __forceinline__ uint32_t z_upper_bound_bits(const TriSetup<T>& s) {
+  const T min_x = min3(s.p0x, s.p1x, s.p2x), min_y = min3(s.p0y, s.p1y, s.p2y);
+  const T max_x = max3(s.p0x, s.p1x, s.p2x), max_y = max3(s.p0y, s.p1y, s.p2y);
+  const T ext = (max_x - min_x > max_y - min_y ? max_x - min_x : max_y - min_y) + T(2);
+  const T eps = sizeof(T) == 4 ? T(5.97e-8) : T(1.12e-16);
+  const T delta = T(40) * eps * ext * ext / s.abs_denom + T(2e-6);
+  if (!(delta < T(0.25))) return 0xFFFFFFFFu;
+  const T zb = (T(1) / min3(s.dinv0, s.dinv1, s.dinv2)) / (T(1) - delta);
+  const float hi = static_cast<float>(zb);
+  if (!(hi > 0.0f && hi < 1e30f)) return 0xFFFFFFFFu;
+  return __float_as_uint(hi) + 8u; // 8 ulps above, against the rounding of `hi` itself
 }
 
 // Culling + bounding box only (used by the binning passes).  Returns false if the triangle is
@@ -788,9 +810,12 @@ using TriOwn = TriRow<T>;
 // workgroup (cooperative pass over a large triangle, `lane16_half` = thread id + 1/2).
 // FM (round 6; before: a second library built with -DDRTK_DEPTH_FASTMATH_ORDER): the order of the depth sum, chosen per
 // LAUNCH from the library's depth-order setting (drtk_amd_set_depth_order / DRTK_AMD_DEPTH_ORDER, include/drtk_amd.h).
-template <typename T, int TILE_SHIFT, bool EARLY_Z, bool FM, int STRIDE = 16>
+// PEEL (rasterize_layers, layers >= 1): `zthr` holds the previous layer's key of every pixel of the item (~0: the pixel
+// has no further fragment), and only fragments whose key is strictly greater compete for the minimum.
+template <typename T, int TILE_SHIFT, bool EARLY_Z, bool FM, bool PEEL, int STRIDE = 16>
 __device__ __forceinline__ void shade_rows(
-    const TriRow<T>& u, float lane16_half, float x0f, float y0f, unsigned long long* __restrict__ zbuf, int dbg) {
+    const TriRow<T>& u, float lane16_half, float x0f, float y0f, unsigned long long* __restrict__ zbuf,
+    const unsigned long long* __restrict__ zthr, int dbg) {
   constexpr float kTileF = static_cast<float>(1 << TILE_SHIFT);
   const float rx0f = static_cast<float>(u.box & 63), ry0f = static_cast<float>((u.box >> 6) & 63);
   const float bwf = static_cast<float>(((u.box >> 12) & 63) + 1), bhf = static_cast<float>(((u.box >> 18) & 63) + 1);
@@ -838,6 +863,14 @@ __device__ __forceinline__ void shade_rows(
     const T b2 = (py - u.ay[2]) * u.dx[2] - (px - u.ax[2]) * u.dy[2];
     if (!((b0 >= thr0) & (b1 >= thr1) & (b2 >= thr2))) continue;
     const int zi = static_cast<int>(__builtin_fmaf(fly, kTileF, c0f) + flx);
+    unsigned long long thr = 0;
+    if constexpr (PEEL) {
+      thr = zthr[zi];
+      if (thr == ~0ull) continue; // the previous layer is empty here: so is this one
+      // the previous layer's fragment of this pixel IS this triangle's (a triangle has one fragment per pixel, and the
+      // arithmetic below would reproduce its key bit for bit): rejected without the depth arithmetic
+      if (static_cast<uint32_t>(thr) == static_cast<uint32_t>(id)) continue;
+    }
     if (EARLY_Z) {
       // second group only: a fragment whose triangle cannot be nearer than what the pixel already holds -- the
       // rigorous bound against the stored depth, strictly, as in the block test -- skips the depth arithmetic (two
@@ -880,14 +913,18 @@ __device__ __forceinline__ void shade_rows(
     if (__ballot(!fast_rcp_ok_clamped(di)) != 0) rd = exact_rcp(di);
     const float depth = static_cast<float>(rd);
     const unsigned long long packed = (static_cast<unsigned long long>(__float_as_uint(depth)) << 32) | id;
+    if constexpr (PEEL) {
+      if (!(packed > thr)) continue; // this fragment belongs to an earlier layer (the whole key decides: depth ties peel by id)
+    }
     atomicMin(&zbuf[zi], packed);
   }
 }
 
 // Rasterize the triangles held one per lane (own-lane state `o`): `nsteps` steps, step k = lane k of every row.
-template <typename T, int TILE_SHIFT, bool EARLY_Z, bool FM>
+template <typename T, int TILE_SHIFT, bool EARLY_Z, bool FM, bool PEEL>
 __device__ __forceinline__ void raster_rows(
-    const TriOwn<T>& o, int nsteps, int x0, int y0, unsigned long long* __restrict__ zbuf, int dbg) {
+    const TriOwn<T>& o, int nsteps, int x0, int y0, unsigned long long* __restrict__ zbuf,
+    const unsigned long long* __restrict__ zthr, int dbg) {
   const float x0f = static_cast<float>(x0), y0f = static_cast<float>(y0);
   const float lane16_half = static_cast<float>(lane_id() & 15) + 0.5f;
   for (int k = 0; k < nsteps; ++k) {
@@ -900,7 +937,7 @@ __device__ __forceinline__ void raster_rows(
       default: u = row_bcast_tri<15>(o); break;
 #undef DRTK_ROW_STEP
     }
-    shade_rows<T, TILE_SHIFT, EARLY_Z, FM>(u, lane16_half, x0f, y0f, zbuf, dbg);
+    shade_rows<T, TILE_SHIFT, EARLY_Z, FM, PEEL>(u, lane16_half, x0f, y0f, zbuf, zthr, dbg);
   }
 }
 
@@ -915,9 +952,15 @@ __device__ __forceinline__ void raster_rows(
 #endif                        // 0.305 / 0.36 at 100k / 250k triangles -- a wave-group holds ~3.4 triangles either way
 constexpr int kRasterBlock = DRTK_RASTER_BLOCK;
 constexpr int kRasterWaves = kRasterBlock / kWave;
-template <typename T>
+// What a raster kernel instantiation is for.  kPlain: `rasterize` ([N,H,W] images).  The two others serve rasterize_layers
+// ([N,K,H,W] images): kLayerFirst draws layer 0 -- the plain kernel with the layered image stride, nothing else -- and
+// kLayerPeel a layer k >= 1, with the previous layer's keys as a per-pixel threshold in a second LDS tile.
+constexpr int kPlain = 0, kLayerFirst = 1, kLayerPeel = 2;
+template <typename T, int MODE = kPlain>
 constexpr int raster_waves_per_simd() { // double: twice the registers per value (134 VGPRs) -> ONE workgroup (2 waves per
-  return sizeof(T) == 4 ? DRTK_RASTER_WAVES_PER_SIMD : 2; // SIMD) per CU; bounded to 128 for two it spills
+  // SIMD) per CU; bounded to 128 for two it spills.  kLayerPeel, float: the second 32 KiB tile leaves room for TWO
+  // workgroups per CU by LDS (2 x 80 KB of 160 KiB), hence 4 waves per SIMD
+  return sizeof(T) == 4 ? (MODE == kLayerPeel ? (DRTK_RASTER_WAVES_PER_SIMD < 4 ? DRTK_RASTER_WAVES_PER_SIMD : 4) : DRTK_RASTER_WAVES_PER_SIMD) : 2;
 }
 constexpr int kIdRing = 128; // accepted triangle ids waiting for set-up, per wave (power of two, >= 2 * kWave - 1)
 // Cooperative pass.  A 16-lane row walks its triangle's clipped bbox 16 pixels a pass, whatever the size: a triangle that
@@ -944,18 +987,29 @@ constexpr int kCoopMin = DRTK_RASTER_COOP_MIN, kCoopMinDense = DRTK_RASTER_COOP_
 constexpr int kCoopBatch = 64; // triangles set up together, one per lane of the waves' first lanes, and parked in LDS
 constexpr int kCoopMax = 256; // entries per item and phase; what does not fit takes the ordinary path
 
-template <typename T, int TILE_SHIFT, bool FM>
-__global__ __launch_bounds__(kRasterBlock, raster_waves_per_simd<T>()) void tile_raster_kernel(
+// The body of the raster kernels (tile_raster_kernel, tile_raster_layer_kernel below).  `num_layers`, `layer`: the K of
+// the [N,K,H,W] images and the layer this launch writes (MODE != kPlain only).
+template <typename T, int TILE_SHIFT, bool FM, int MODE>
+__device__ __forceinline__ void tile_raster_body(
     const T* __restrict__ v, const int32_t* __restrict__ vi, int F, int64_t V, int64_t vi_sN,
     int H, int W, int tiles_x, int tiles_per_view, const int32_t* __restrict__ tile_offset,
     const unsigned long long* __restrict__ tile_count, const float* __restrict__ view_stats,
     const int32_t* __restrict__ pairs, const int32_t* __restrict__ big_count,
     const int32_t* __restrict__ big_list, const uint2* __restrict__ tri_range, const uint4* __restrict__ tri_pre,
     const uint32_t* __restrict__ items, int32_t* __restrict__ queue, float* __restrict__ depth_img,
-    int32_t* __restrict__ index_img, int dbg) {
+    int32_t* __restrict__ index_img, int dbg, int num_layers, int layer) {
   constexpr int TILE = 1 << TILE_SHIFT;
   constexpr int NPIX = TILE * TILE;
+  constexpr bool PEEL = MODE == kLayerPeel;
   __shared__ unsigned long long zbuf[NPIX];
+  unsigned long long* zthr = nullptr; // the previous layer's keys of the item's pixels, laid out like zbuf
+  uint32_t* tmin = nullptr;           // ... and the nearest of their depths in every 8x8 block (pixels without one: 0xFFFFFFFF)
+  if constexpr (PEEL) {
+    __shared__ unsigned long long s_zthr[NPIX];
+    __shared__ uint32_t s_tmin[(TILE / 8) * (TILE / 8)];
+    zthr = s_zthr;
+    tmin = s_tmin;
+  }
   __shared__ uint32_t s_zmax[(TILE / 8) * (TILE / 8)];
   __shared__ int32_t s_idq[kRasterWaves][kIdRing];
   __shared__ int32_t s_idk[kRasterWaves][kIdRing]; // ... and the size of what each will have to shade (sort key)
@@ -972,7 +1026,9 @@ __global__ __launch_bounds__(kRasterBlock, raster_waves_per_simd<T>()) void tile
   static_assert(kCoopBatch % kRasterWaves == 0 && kCoopBatch / kRasterWaves <= kWave, "cooperative batch set-up needs kRasterWaves | kCoopBatch");
   static_assert(
       (sizeof(unsigned long long) * NPIX + sizeof(uint32_t) * (TILE / 8) * (TILE / 8) + 2 * sizeof(int32_t) * kRasterWaves * kIdRing +
-       sizeof(int32_t) * kCoopMax + sizeof(uint32_t) * kCoopBatch * kTriWords + 64) * (raster_waves_per_simd<T>() * 4 / kRasterWaves > 0 ? raster_waves_per_simd<T>() * 4 / kRasterWaves : 1) <= 160 * 1024,
+       sizeof(int32_t) * kCoopMax + sizeof(uint32_t) * kCoopBatch * kTriWords + 64 +
+       (PEEL ? sizeof(unsigned long long) * NPIX + sizeof(uint32_t) * (TILE / 8) * (TILE / 8) : 0)) *
+              (raster_waves_per_simd<T, MODE>() * 4 / kRasterWaves > 0 ? raster_waves_per_simd<T, MODE>() * 4 / kRasterWaves : 1) <= 160 * 1024,
       "tile_raster's static LDS no longer fits the workgroups per CU its launch bounds ask for");
 
   const int tid = threadIdx.x;
@@ -1024,13 +1080,78 @@ __global__ __launch_bounds__(kRasterBlock, raster_waves_per_simd<T>()) void tile
     {
       const int rows = y1 - y0 + 1;
       const int nbig = big_count[n];
-      const int64_t img_base = int64_t(n) * H * W;
+      int64_t img_base_of_item = int64_t(n) * H * W;
+      if constexpr (MODE != kPlain) img_base_of_item = (int64_t(n) * num_layers + layer) * H * W;
+      const int64_t img_base = img_base_of_item;
       const bool vec_ok = (W & 3) == 0;
       // 16-byte stores that need the element's alignment only (rows of any width, output views at any element offset)
       typedef int32_t IQuad __attribute__((ext_vector_type(4), aligned(4)));
       typedef float FQuad __attribute__((ext_vector_type(4), aligned(4)));
       const int quads_per_row = ss >> 2;
-      if ((item & kItemEmpty) && nbig == 0) {
+      bool exhausted = false;
+      if constexpr (PEEL) {
+        // The threshold of every pixel of the item's rectangle: the key the previous layer stored (one plane before
+        // this one in the [N,K,H,W] images), ~0 where it is empty.  A rectangle whose previous layer is empty
+        // everywhere has no further fragment at all: this layer is background there, like a tile with an empty list.
+        if (!((item & kItemEmpty) && nbig == 0)) {
+          const int ss_log = TILE_SHIFT - split_log;
+          const int64_t prev_base = img_base - int64_t(H) * W;
+          int any = 0;
+          // four pixels per thread, like the store sweep (16-byte loads that need the element's alignment only); the
+          // depth is read only where a pixel of the quad has a fragment; off the canvas: ~0, like an empty pixel
+          typedef int32_t IQuadIn __attribute__((ext_vector_type(4), aligned(4)));
+          typedef float FQuadIn __attribute__((ext_vector_type(4), aligned(4)));
+          for (int q = tid; q < (ss << (ss_log - 2)); q += kRasterBlock) {
+            const int row = q >> (ss_log - 2), col = (q & ((ss >> 2) - 1)) << 2;
+            int32_t pi[4] = {-1, -1, -1, -1};
+            float pd[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            const int x = x0 + col;
+            if (row < rows && x <= x1) {
+              const int64_t o = prev_base + int64_t(y0 + row) * W + x;
+              const bool whole = vec_ok || x + 3 <= x1;
+              if (whole) {
+                const IQuadIn iq = *reinterpret_cast<const IQuadIn*>(index_img + o);
+                pi[0] = iq.x, pi[1] = iq.y, pi[2] = iq.z, pi[3] = iq.w;
+              } else {
+                for (int j = 0; j < 4 && x + j <= x1; ++j) pi[j] = index_img[o + j];
+              }
+              if ((pi[0] & pi[1] & pi[2] & pi[3]) >= 0) { // some index of the quad is not negative
+                any = 1;
+                if (whole) {
+                  const FQuadIn dq = *reinterpret_cast<const FQuadIn*>(depth_img + o);
+                  pd[0] = dq.x, pd[1] = dq.y, pd[2] = dq.z, pd[3] = dq.w;
+                } else {
+                  for (int j = 0; j < 4 && x + j <= x1; ++j) pd[j] = depth_img[o + j];
+                }
+              }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              zthr[(row << TILE_SHIFT) + col + j] =
+                  pi[j] < 0 ? ~0ull : ((static_cast<unsigned long long>(__float_as_uint(pd[j])) << 32) | static_cast<uint32_t>(pi[j]));
+            }
+          }
+          exhausted = __syncthreads_or(any) == 0; // (also: the thresholds are in place before any wave reads them)
+          if (!exhausted) {
+            // nearest threshold of every 8x8 block, like the farthest depth below: a wave takes a row of blocks, lane =
+            // pixel column, eight rows per lane, then the minimum over each group of 8 lanes
+            const int nb_thr = ss >> 3;
+            for (int by = wave; by < nb_thr; by += kRasterWaves) {
+              uint32_t m = 0xFFFFFFFFu;
+              if (lane < ss) {
+#pragma unroll
+                for (int r = 0; r < 8; ++r) m = min(m, static_cast<uint32_t>(zthr[(((by << 3) + r) << TILE_SHIFT) + lane] >> 32));
+              }
+              m = min(m, static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(m), 0xB1, 0xF, 0xF, true)));  // quad_perm [1,0,3,2]
+              m = min(m, static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(m), 0x4E, 0xF, 0xF, true)));  // quad_perm [2,3,0,1]
+              m = min(m, static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(m), 0x141, 0xF, 0xF, true))); // row_half_mirror
+              if ((lane & 7) == 0 && lane < ss) tmin[by * nb_thr + (lane >> 3)] = m;
+            }
+            __syncthreads();
+          }
+        }
+      }
+      if (((item & kItemEmpty) && nbig == 0) || exhausted) {
         // nothing can touch this tile: background straight to the images, no LDS tile, no barrier
         for (int q = tid; q < rows * quads_per_row; q += kRasterBlock) {
           const int row = q / quads_per_row;
@@ -1207,13 +1328,29 @@ __global__ __launch_bounds__(kRasterBlock, raster_waves_per_simd<T>()) void tile
             z_lo = pre.z;
             valid = tri_setup<T>(v_n, vi_n + int64_t(f) * 3, H, W, s);
             if (valid && pre.w == 0u) valid = accept(s.bb_min_x, s.bb_min_y, s.bb_max_x, s.bb_max_y, 0u);
+            if constexpr (PEEL) {
+              // A triangle whose depth UPPER bound lies below the nearest threshold of all 8x8 blocks its clipped bbox
+              // touches has every fragment in an earlier layer (pixels without a threshold take none): not shaded.
+              // Strict on the depth bits alone, so ties -- which peel by id -- are never decided here.
+              if (valid) {
+                const uint32_t z_hi = z_upper_bound_bits<T>(s);
+                const int cx0 = (max(s.bb_min_x, x0) - x0) >> 3, cx1 = (min(s.bb_max_x, x1) - x0) >> 3;
+                const int cy0 = (max(s.bb_min_y, y0) - y0) >> 3, cy1 = (min(s.bb_max_y, y1) - y0) >> 3;
+                if (cx0 <= cx1 && cy0 <= cy1 && (cx1 - cx0 + 1) * (cy1 - cy0 + 1) <= 16) {
+                  uint32_t near = 0xFFFFFFFFu;
+                  for (int by = cy0; by <= cy1; ++by)
+                    for (int bx = cx0; bx <= cx1; ++bx) near = min(near, tmin[by * nb + bx]);
+                  valid = !(z_hi < near);
+                }
+              }
+            }
           }
           const TriOwn<T> own = make_row_state<T>(valid, s, f, z_lo, x0, y0, x1, y1);
           if (!DRTK_DBG(dbg, 1)) {
             if (phase == 0) {
-              raster_rows<T, TILE_SHIFT, false, FM>(own, (cnt + 3) >> 2, x0, y0, zbuf, dbg);
+              raster_rows<T, TILE_SHIFT, false, FM, PEEL>(own, (cnt + 3) >> 2, x0, y0, zbuf, zthr, dbg);
             } else {
-              raster_rows<T, TILE_SHIFT, true, FM>(own, (cnt + 3) >> 2, x0, y0, zbuf, dbg);
+              raster_rows<T, TILE_SHIFT, true, FM, PEEL>(own, (cnt + 3) >> 2, x0, y0, zbuf, zthr, dbg);
             }
           }
         }
@@ -1252,9 +1389,9 @@ __global__ __launch_bounds__(kRasterBlock, raster_waves_per_simd<T>()) void tile
               __builtin_memcpy(&u, w, sizeof(u));
               if (!DRTK_DBG(dbg, 1)) {
                 if (phase == 0) {
-                  shade_rows<T, TILE_SHIFT, false, FM, kRasterBlock>(u, first, x0f, y0f, zbuf, dbg);
+                  shade_rows<T, TILE_SHIFT, false, FM, PEEL, kRasterBlock>(u, first, x0f, y0f, zbuf, zthr, dbg);
                 } else {
-                  shade_rows<T, TILE_SHIFT, true, FM, kRasterBlock>(u, first, x0f, y0f, zbuf, dbg);
+                  shade_rows<T, TILE_SHIFT, true, FM, PEEL, kRasterBlock>(u, first, x0f, y0f, zbuf, zthr, dbg);
                 }
               }
             }
@@ -1329,6 +1466,37 @@ __global__ __launch_bounds__(kRasterBlock, raster_waves_per_simd<T>()) void tile
   }
 }
 
+template <typename T, int TILE_SHIFT, bool FM>
+__global__ __launch_bounds__(kRasterBlock, raster_waves_per_simd<T>()) void tile_raster_kernel(
+    const T* __restrict__ v, const int32_t* __restrict__ vi, int F, int64_t V, int64_t vi_sN,
+    int H, int W, int tiles_x, int tiles_per_view, const int32_t* __restrict__ tile_offset,
+    const unsigned long long* __restrict__ tile_count, const float* __restrict__ view_stats,
+    const int32_t* __restrict__ pairs, const int32_t* __restrict__ big_count,
+    const int32_t* __restrict__ big_list, const uint2* __restrict__ tri_range, const uint4* __restrict__ tri_pre,
+    const uint32_t* __restrict__ items, int32_t* __restrict__ queue, float* __restrict__ depth_img,
+    int32_t* __restrict__ index_img, int dbg) {
+  tile_raster_body<T, TILE_SHIFT, FM, kPlain>(
+      v, vi, F, V, vi_sN, H, W, tiles_x, tiles_per_view, tile_offset, tile_count, view_stats, pairs, big_count, big_list,
+      tri_range, tri_pre, items, queue, depth_img, index_img, dbg, 1, 0);
+}
+
+// rasterize_layers: layer `layer` of `num_layers` into the [N,K,H,W] images, from the bins of the call (built once).
+// MODE = kLayerFirst for layer 0, kLayerPeel for the others, which read layer - 1 (written by the launch before).
+template <typename T, int TILE_SHIFT, bool FM, int MODE>
+__global__ __launch_bounds__(kRasterBlock, (raster_waves_per_simd<T, MODE>())) void tile_raster_layer_kernel(
+    const T* __restrict__ v, const int32_t* __restrict__ vi, int F, int64_t V, int64_t vi_sN,
+    int H, int W, int tiles_x, int tiles_per_view, const int32_t* __restrict__ tile_offset,
+    const unsigned long long* __restrict__ tile_count, const float* __restrict__ view_stats,
+    const int32_t* __restrict__ pairs, const int32_t* __restrict__ big_count,
+    const int32_t* __restrict__ big_list, const uint2* __restrict__ tri_range, const uint4* __restrict__ tri_pre,
+    const uint32_t* __restrict__ items, int32_t* __restrict__ queue, float* __restrict__ depth_img,
+    int32_t* __restrict__ index_img, int dbg, int num_layers, int layer) {
+  static_assert(MODE == kLayerFirst || MODE == kLayerPeel, "the plain mode is tile_raster_kernel");
+  tile_raster_body<T, TILE_SHIFT, FM, MODE>(
+      v, vi, F, V, vi_sN, H, W, tiles_x, tiles_per_view, tile_offset, tile_count, view_stats, pairs, big_count, big_list,
+      tri_range, tri_pre, items, queue, depth_img, index_img, dbg, num_layers, layer);
+}
+
 // Diagnostics: exact_div against the IEEE division on pseudo-random operands.
 template <typename T>
 __global__ __launch_bounds__(kBlock) void exact_div_selftest_kernel(
@@ -1377,14 +1545,18 @@ __global__ __launch_bounds__(kBlock) void exact_div_selftest_kernel(
   if (local) atomicAdd(mismatches, local);
 }
 
+// num_layers == 0: `rasterize` ([N,H,W] images).  num_layers >= 1: rasterize_layers ([N,K,H,W] images): the bins are
+// built once, then one raster launch per layer, each on the same work list with the queue's heads rewound; layer k >= 1
+// reads layer k - 1 from the images as its threshold (stream order makes it visible).
 template <typename T>
 int rasterize_impl(
     const T* v, const int32_t* vi, int64_t N, int64_t V, int64_t F, int64_t vi_sN, int64_t H,
     int64_t W, float* depth_img, int32_t* index_img, void* workspace, size_t workspace_bytes,
-    hipStream_t stream) {
+    hipStream_t stream, int num_layers = 0) {
   const BinLayout L = make_layout(N, F, H, W);
   if (workspace_bytes < L.total_bytes) return DRTK_ERR_WORKSPACE_TOO_SMALL;
   if (N * H * W == 0) return DRTK_OK;
+  if (num_layers == 1) num_layers = 0; // [N,1,H,W] is [N,H,W]: the plain kernel
   char* ws = static_cast<char*>(workspace);
   auto* tile_count = reinterpret_cast<unsigned long long*>(ws + L.off_count);
   auto* tile_cursor = reinterpret_cast<unsigned long long*>(ws + L.off_cursor);
@@ -1431,13 +1603,42 @@ int rasterize_impl(
       (int)H, (int)W, L.tiles_x, (int)L.tiles_per_view, tile_offset, tile_count, view_stats, pairs, big_count,    \
       big_list, tri_range, tri_pre, items, queue, depth_img, index_img, debug_flags())
   const bool fm = depth_order_setting() == DRTK_DEPTH_ORDER_FASTMATH;
-  if (L.tile_shift == 6) {
-    if (fm) DRTK_RASTER_LAUNCH(6, true); else DRTK_RASTER_LAUNCH(6, false);
-  } else {
-    if (fm) DRTK_RASTER_LAUNCH(5, true); else DRTK_RASTER_LAUNCH(5, false);
+  if (num_layers == 0) {
+    if (L.tile_shift == 6) {
+      if (fm) DRTK_RASTER_LAUNCH(6, true); else DRTK_RASTER_LAUNCH(6, false);
+    } else {
+      if (fm) DRTK_RASTER_LAUNCH(5, true); else DRTK_RASTER_LAUNCH(5, false);
+    }
+    DRTK_RETURN_IF_LAUNCH_FAILED();
+    return DRTK_OK;
   }
 #undef DRTK_RASTER_LAUNCH
-  DRTK_RETURN_IF_LAUNCH_FAILED();
+  const unsigned peel_blocks =
+      static_cast<unsigned>(std::min<int64_t>(L.max_items, int64_t(num_compute_units()) * (raster_waves_per_simd<T, kLayerPeel>() / 2)));
+#define DRTK_LAYER_LAUNCH(SHIFT, FM, MODE, BLOCKS)                                                                 \
+  DRTK_LAUNCH(                                                                                                    \
+      (tile_raster_layer_kernel<T, SHIFT, FM, MODE>), dim3(BLOCKS), dim3(kRasterBlock), 0, stream, v, vi, (int)F, V, \
+      vi_sN, (int)H, (int)W, L.tiles_x, (int)L.tiles_per_view, tile_offset, tile_count, view_stats, pairs, big_count, \
+      big_list, tri_range, tri_pre, items, queue, depth_img, index_img, debug_flags(), num_layers, layer)
+  for (int layer = 0; layer < num_layers; ++layer) {
+    if (layer == 0) {
+      if (L.tile_shift == 6) {
+        if (fm) DRTK_LAYER_LAUNCH(6, true, kLayerFirst, blocks); else DRTK_LAYER_LAUNCH(6, false, kLayerFirst, blocks);
+      } else {
+        if (fm) DRTK_LAYER_LAUNCH(5, true, kLayerFirst, blocks); else DRTK_LAYER_LAUNCH(5, false, kLayerFirst, blocks);
+      }
+    } else {
+      // rewind the shards' heads (queue[1], the number of items, stays): the same work list serves every layer
+      if (fill_bytes_async(queue + kQueueStride, 0, sizeof(int32_t) * kQueueStride * kQueueShards, stream) != DRTK_OK) return DRTK_ERR_LAUNCH;
+      if (L.tile_shift == 6) {
+        if (fm) DRTK_LAYER_LAUNCH(6, true, kLayerPeel, peel_blocks); else DRTK_LAYER_LAUNCH(6, false, kLayerPeel, peel_blocks);
+      } else {
+        if (fm) DRTK_LAYER_LAUNCH(5, true, kLayerPeel, peel_blocks); else DRTK_LAYER_LAUNCH(5, false, kLayerPeel, peel_blocks);
+      }
+    }
+    DRTK_RETURN_IF_LAUNCH_FAILED();
+  }
+#undef DRTK_LAYER_LAUNCH
   return DRTK_OK;
 }
 
@@ -1498,6 +1699,40 @@ extern "C" int drtk_amd_rasterize(
     default:
       return DRTK_ERR_INVALID_ARGUMENT;
   }
+}
+
+extern "C" int drtk_amd_rasterize_layers_workspace_bytes(
+    int64_t N, int64_t F, int64_t H, int64_t W, int num_layers, size_t* bytes) {
+  if (!bytes || N < 0 || F < 0 || H <= 0 || W <= 0 || num_layers < 1 || num_layers > DRTK_AMD_MAX_RASTER_LAYERS) return DRTK_ERR_INVALID_ARGUMENT;
+  *bytes = make_layout(N, F, H, W).total_bytes; // the bins, shared by all layers: the thresholds live in the images
+  return DRTK_OK;
+}
+
+extern "C" int drtk_amd_rasterize_layers(
+    drtk_dtype_t dtype, const void* v, const int32_t* vi, int64_t N, int64_t V, int64_t F,
+    int64_t vi_sN, int64_t H, int64_t W, int num_layers, float* depth_img, int32_t* index_img,
+    void* workspace, size_t workspace_bytes, drtk_stream_t stream) {
+  if (num_layers < 1 || num_layers > DRTK_AMD_MAX_RASTER_LAYERS) return DRTK_ERR_INVALID_ARGUMENT;
+  if (N < 0 || V < 0 || F < 0 || H <= 0 || W <= 0) return DRTK_ERR_INVALID_ARGUMENT;
+  if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return DRTK_ERR_INVALID_ARGUMENT;
+  if (V >= 0x10000000LL) return DRTK_ERR_TOO_MANY_VERTICES;
+  if (dtype != DRTK_F32 && dtype != DRTK_F64) return DRTK_ERR_INVALID_ARGUMENT;
+  if (vi_sN != 0 && vi_sN != F * 3) return DRTK_ERR_INVALID_ARGUMENT;
+  const int64_t K = num_layers;
+  // more views than one launch takes: slices, each reusing the workspace (sized for all N: enough for any slice)
+  DRTK_FOR_VIEW_SLICES(N, n0, n, drtk_amd_rasterize_layers(
+      dtype, advance(v, n0 * V * 3, dtype_size(dtype)), advance_typed(vi, n0 * vi_sN), n, V, F, vi_sN, H, W, num_layers,
+      advance_typed(depth_img, n0 * K * H * W), advance_typed(index_img, n0 * K * H * W), workspace, workspace_bytes, stream))
+  if (H > 65535LL * 32 || W > 65535LL * 32 || N * F >= (int64_t(1) << 31) / kMaxSmallTiles ||
+      N * K * H * W >= (int64_t(1) << 40))
+    return DRTK_ERR_INVALID_ARGUMENT;
+  if (N * H * W > 0 && (!depth_img || !index_img || !workspace)) return DRTK_ERR_INVALID_ARGUMENT;
+  // Triangles need vertices, as in drtk_amd_rasterize
+  if (N * F > 0 && (!v || !vi)) return DRTK_ERR_INVALID_ARGUMENT;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (dtype == DRTK_F32)
+    return rasterize_impl<float>(static_cast<const float*>(v), vi, N, V, F, vi_sN, H, W, depth_img, index_img, workspace, workspace_bytes, s, num_layers);
+  return rasterize_impl<double>(static_cast<const double*>(v), vi, N, V, F, vi_sN, H, W, depth_img, index_img, workspace, workspace_bytes, s, num_layers);
 }
 
 extern "C" int drtk_amd_selftest_exact_div(

@@ -1,4 +1,5 @@
-"""`rasterize` / `rasterize_with_depth` -- host-side mirror of drtk/rasterize.py:17-103."""
+"""`rasterize` / `rasterize_with_depth` -- host-side mirror of drtk/rasterize.py:17-103 -- and this package's
+`rasterize_layers` / `rasterize_layers_with_depth` (the K nearest triangles per pixel)."""
 import ctypes
 from typing import Tuple
 
@@ -81,5 +82,52 @@ def rasterize_with_depth(
     depth; empty pixels hold 0.  Returns `(depth_img, index_img)` (drtk/rasterize.py:68-103)."""
     depth_img, index_img = th.ops.rasterize_ext.rasterize(
         v, _batched_vi(vi, v.shape[0]), height, width, wireframe
+    )
+    return depth_img, index_img
+
+
+MAX_RASTER_LAYERS = 8  # DRTK_AMD_MAX_RASTER_LAYERS (include/drtk_amd.h)
+
+
+@th.compiler.disable
+def rasterize_layers(
+    v: th.Tensor,
+    vi: th.Tensor,
+    height: int,
+    width: int,
+    num_layers: int,
+) -> th.Tensor:
+    """The `num_layers` nearest triangles of every pixel (depth peeling), triangle mode.
+
+    A pixel's fragments are the triangles :func:`rasterize` would consider covering its centre, ordered by
+    the key `(float32 depth bits << 32) | triangle id` as an unsigned 64-bit number; layer `k` is the k-th of them.
+    Layer 0 is :func:`rasterize` bit for bit, keys increase strictly with `k`, fragments of equal depth all appear
+    (lower id first), and layers a pixel has no fragment for hold `-1`.
+
+    Args:
+        v, vi, height, width: as for :func:`rasterize`.
+        num_layers: `1 <= num_layers <= 8`.
+
+    Returns:
+        `index_img [N, K, H, W]` int32.  Not differentiable.  To shade the layers fold them into the batch --
+        `index_img.flatten(0, 1)` with `v.repeat_interleave(K, 0)` goes through `render` / `interpolate` as it is --
+        and composite front to back.
+    """
+    _, index_img = th.ops.drtk_amd_ext.rasterize_layers(v, _batched_vi(vi, v.shape[0]), height, width, num_layers)
+    return index_img
+
+
+@th.compiler.disable
+def rasterize_layers_with_depth(
+    v: th.Tensor,
+    vi: th.Tensor,
+    height: int,
+    width: int,
+    num_layers: int,
+) -> Tuple[th.Tensor, th.Tensor]:
+    """Like :func:`rasterize_layers` but also returns the (non-differentiable, always float32) depth of every layer,
+    0 where the layer is empty.  Returns `(depth_img, index_img)`, both `[N, K, H, W]`."""
+    depth_img, index_img = th.ops.drtk_amd_ext.rasterize_layers(
+        v, _batched_vi(vi, v.shape[0]), height, width, num_layers
     )
     return depth_img, index_img

@@ -120,6 +120,30 @@ int drtk_amd_rasterize(
     void* workspace, size_t workspace_bytes, drtk_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * rasterize_layers     (no counterpart in the reference: its z-buffer keeps the nearest fragment only)
+ *
+ * The `num_layers` nearest triangles of every pixel in one call (depth peeling), triangle mode only.  The FRAGMENTS of
+ * a pixel are the triangles drtk_amd_rasterize would consider covering its centre (same culling, top-left rule, exact
+ * arithmetic, depth expression under the current depth-order setting), each with the key
+ * (float32 depth bits << 32) | triangle id, an unsigned 64-bit number.  Layer k (0-based) of a pixel is its fragment
+ * with the k-th smallest key:
+ *     index_img [N,K,H,W] int32   its id, -1 where the pixel has fewer than k + 1 fragments
+ *     depth_img [N,K,H,W] float32 its depth, 0 there
+ * Layer 0 is drtk_amd_rasterize bit for bit; keys increase strictly with k, empty layers trail; fragments of equal
+ * depth all appear, lower id first.  Deterministic.  1 <= num_layers <= DRTK_AMD_MAX_RASTER_LAYERS, checked before
+ * anything else.  The workspace holds the tile bins, built once per call and shared by all layers (same size as
+ * drtk_amd_rasterize's); the call only enqueues (num_layers raster launches) and can be captured into a graph.
+ * To shade the layers, fold them into the batch: index_img viewed as [N*K,H,W] with every view's vertices
+ * repeated K times goes through render / interpolate unchanged ("layers").
+ */
+#define DRTK_AMD_MAX_RASTER_LAYERS 8
+int drtk_amd_rasterize_layers_workspace_bytes(int64_t N, int64_t F, int64_t H, int64_t W, int num_layers, size_t* bytes);
+int drtk_amd_rasterize_layers(
+    drtk_dtype_t dtype, const void* v, const int32_t* vi, int64_t N, int64_t V, int64_t F,
+    int64_t vi_sN, int64_t H, int64_t W, int num_layers, float* depth_img, int32_t* index_img,
+    void* workspace, size_t workspace_bytes, drtk_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * render           replaces render_cuda               (src/render/render_kernel.cu:283-380)
  * Perspective-correct barycentrics + depth per pixel; zeros where index_img == -1.
  */
