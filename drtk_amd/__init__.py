@@ -12,6 +12,7 @@ from drtk_amd.geometry import (  # noqa: F401
     vert_normals,
 )
 from drtk_amd.graph import capture_step  # noqa: F401
+from drtk_amd.grid_scatter import grid_scatter  # noqa: F401
 from drtk_amd.interpolate import (  # noqa: F401
     interpolate,
     interpolate_masked,
@@ -38,8 +39,9 @@ __version__ = "0.1.0"
 # HIP graph) and `set_depth_order` / `get_depth_order` (the rasterizer's depth order: the reference's source, or the
 # reference as its setup.py builds it) and `rasterize_layers` / `rasterize_layers_with_depth` (the K nearest triangles per
 # pixel, for front-to-back compositing) are this package's additions.  The mesh geometry of drtk.utils (face_info,
-# vert_normals, face_attribute_to_vert, face_dpdt, vert_binormals) is exported here too.  Not
-# provided: grid_scatter, msi, filter2d and the pure-PyTorch `*_ref` models (out of scope).
+# vert_normals, face_attribute_to_vert, face_dpdt, vert_binormals) is exported here too, and so is `grid_scatter` (the
+# splatting counterpart of grid_sample; the `drtk` drop-in package does not lift it yet -- INTEGRATION.md).  Not
+# provided: msi, filter2d and the pure-PyTorch `*_ref` models (out of scope).
 __all__ = [
     "rasterize",
     "rasterize_with_depth",
@@ -52,6 +54,7 @@ __all__ = [
     "interpolation_matrix",
     "interpolation_normal_matrix",
     "mipmap_grid_sample",
+    "grid_scatter",
     "screen_space_uv_derivative",
     "transform",
     "transform_with_v_cam",

@@ -146,6 +146,8 @@ EXPORTS = [
     "drtk_amd_interpolation_normal_matrix_values_backward",
     "drtk_amd_mipmap_grid_sampler_2d",
     "drtk_amd_mipmap_grid_sampler_2d_backward",
+    "drtk_amd_grid_scatter_2d",
+    "drtk_amd_grid_scatter_2d_backward",
     "drtk_amd_screen_space_uv_derivative",
     "drtk_amd_transform_pinhole",
     "drtk_amd_transform_pinhole_backward",
@@ -551,6 +553,53 @@ def mipmap_grid_sampler_2d_backward(grad_out, levels, grid, vt_dxdy_img, max_ani
             gptrs, _p(ggrid), glayout, _stream(lv[0], stream)),
         "mipmap_grid_sampler_2d_backward")
     return glv, ggrid
+
+
+@_on_tensor_device
+def grid_scatter_2d(input, grid, output_height, output_width, padding_mode=1, interpolation_mode=0, align_corners=False,
+                    stream=None, route_counts=None):
+    """out [N,C,output_height,output_width]: every pixel of input [N,C,H,W] added, weighted, to the texels grid_sample
+    would read at grid [N,H,W,2].  `route_counts`: an int32 / uint32 device tensor of two ZEROED counters that receives
+    the number of workgroups per kernel route (windowed, direct) -- include/drtk_amd.h."""
+    input = input.contiguous()
+    grid, glayout = _grid_layout(grid)
+    N, C, H, W = input.shape
+    assert grid.shape == (N, H, W, 2) and grid.dtype == input.dtype, (grid.shape, input.shape)
+    if route_counts is not None:
+        assert route_counts.numel() == 2 and route_counts.element_size() == 4 and route_counts.is_contiguous() and route_counts.device == input.device
+    out = _out(N, C, int(output_height), int(output_width), dtype=input.dtype, device=input.device)
+    _check(
+        lib().drtk_amd_grid_scatter_2d(
+            ctypes.c_int(_dt(input)), _p(input), _p(grid), glayout, _i(N), _i(C), _i(H), _i(W), _i(output_height),
+            _i(output_width), ctypes.c_int(padding_mode), ctypes.c_int(interpolation_mode), ctypes.c_int(bool(align_corners)),
+            _p(out), _p(route_counts), _stream(input, stream)),
+        "grid_scatter_2d")
+    return out
+
+
+@_on_tensor_device
+def grid_scatter_2d_backward(grad_out, input, grid, padding_mode=1, interpolation_mode=0, align_corners=False,
+                             input_requires_grad=True, grid_requires_grad=True, stream=None):
+    """(grad_input [N,C,H,W] or None, grad_grid laid out like `grid` or None)."""
+    input = input.contiguous()
+    grad_out = grad_out.contiguous()
+    grid, glayout = _grid_layout(grid)
+    N, C, H, W = input.shape
+    OH, OW = grad_out.shape[2:]
+    assert grad_out.shape[:2] == (N, C) and grid.shape == (N, H, W, 2)
+    gi = _out(N, C, H, W, dtype=input.dtype, device=input.device) if input_requires_grad else None
+    gg = None
+    if grid_requires_grad:  # laid out like the grid it belongs to
+        gg = th.empty_strided(grid.shape, grid.stride(), dtype=grid.dtype, device=grid.device)
+        if _POISON and gg.numel():
+            gg.fill_(float("nan"))
+    _check(
+        lib().drtk_amd_grid_scatter_2d_backward(
+            ctypes.c_int(_dt(input)), _p(grad_out), _p(input), _p(grid), glayout, _i(N), _i(C), _i(H), _i(W), _i(OH), _i(OW),
+            ctypes.c_int(padding_mode), ctypes.c_int(interpolation_mode), ctypes.c_int(bool(align_corners)), _p(gi), _p(gg),
+            glayout, _stream(input, stream)),
+        "grid_scatter_2d_backward")
+    return gi, gg
 
 
 @_on_tensor_device

@@ -85,6 +85,30 @@ inline Tensor alloc_workspace(size_t bytes, const Tensor& like) {
   return out_empty({static_cast<int64_t>(bytes)}, like.options().dtype(at::kByte));
 }
 
+// A uv field [N,H,W,2] whose pixels are evenly spaced in memory is read in place: contiguous, or the channel-first image
+// `interpolate` produces seen through permute(0, 2, 3, 1) (the reference reads grid through its strides,
+// mipmap_grid_sampler_kernel.cu:430-445).  Anything else is made contiguous.  layout = {sN, sP, sC} for the C ABI.
+struct GridArg {
+  Tensor t;
+  int64_t layout[3];
+};
+inline GridArg prep_grid(const Tensor& grid) {
+  const int64_t N = grid.size(0), H = grid.size(1), W = grid.size(2), P = H * W;
+  const int64_t sN = grid.stride(0), sH = grid.stride(1), sW = grid.stride(2), sC = grid.stride(3);
+  const bool rows_ok = H <= 1 || sH == W * sW;
+  const bool pixel_major = sC == 1 && sW == 2 && rows_ok && (N <= 1 || sN >= 2 * P);
+  const bool channel_major = sW == 1 && sC >= P && rows_ok && (N <= 1 || sN >= sC + P);
+  GridArg a;
+  if (grid.size(3) == 2 && P > 0 && (pixel_major || channel_major)) {
+    a.t = grid;
+    a.layout[0] = N > 1 ? sN : 2 * P, a.layout[1] = sW, a.layout[2] = sC;
+  } else {
+    a.t = grid.contiguous();
+    a.layout[0] = 2 * P, a.layout[1] = 2, a.layout[2] = 1;
+  }
+  return a;
+}
+
 [[noreturn]] inline void no_cpu(const char* op) {
   TORCH_CHECK(false, op, "(): drtk_amd implements the MI355X (HIP) path only; got CPU tensors");
 }

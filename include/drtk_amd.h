@@ -305,6 +305,41 @@ int drtk_amd_mipmap_grid_sampler_2d_backward(
     void* grad_grid, const int64_t* grad_grid_layout, drtk_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * grid_scatter_2d -- the splatting counterpart of grid_sample: every input pixel ADDS weight * input to the texels
+ * grid_sample would have read at its grid location; replaces grid_scatter_2d_cuda / _cuda_backward
+ * (grid_scatter_kernel.cu:624-788).  Coordinates are grid_sample's: normalised [-1,1], align_corners, padding.
+ *   input        [N,C,H,W] contiguous;  grid [N,H,W,2], read through grid_layout (see mipmap_grid_sampler_2d: NULL =
+ *                contiguous, {2HW, 1, HW} = the channel-first uv image of `interpolate` seen through permute(0,2,3,1))
+ *   out          [N,C,output_height,output_width]; zero-filled here (a fill kernel on `stream`), then accumulated into
+ *   padding_mode 0 zeros | 1 border | 2 reflection;  interpolation_mode 0 bilinear | 2 bicubic
+ *   route_counts NULL, or two device counters the caller has zeroed: the call adds the number of workgroups (tiles of
+ *                16 x 16 input pixels that reach the output at all) that took the windowed route -- the texels of the tile
+ *                fit an LDS window, one global atomic per touched texel, channel and workgroup, in row segments -- to
+ *                [0], and of those that fell back to one global atomic per tap and channel to [1].  The route is chosen
+ *                on the device from the tile's own grid values; the host never reads the grid.  Diagnostics only.
+ * H * W < 2^31 and output_height * output_width < 2^31, both output sizes > 0.  Non-finite grid coordinates add nothing
+ * (zeros padding) or land on a border texel; they never write out of range.
+ * BICUBIC CENTRE RULE: as in the reference, the centre coordinate goes through the whole padding transform (clip, or reflect
+ * and clip) before floor and the fractional part are taken, and each of the sixteen tap indices goes through it again;
+ * torch's grid_sample only unnormalises the centre.  The two differ for border / reflection padding where the unnormalised
+ * coordinate lies outside [0, size - 1]; everywhere else (all bilinear modes, bicubic zeros) out is exactly the adjoint of
+ * grid_sample ("Texture-space scatter").
+ * REPRODUCIBILITY: out is accumulated with float atomics in varying order: equal up to rounding from run to run, not
+ * bitwise (the reference's is atomic-ordered too).  The backward pass is a gather and bit-reproducible.
+ * Backward: grad_input [N,C,H,W] = grid_sample(grad_out, grid) and grad_grid (laid out by grad_grid_layout) =
+ * d/dgrid <grid_sample(grad_out, grid), input>; either may be NULL (not computed), what is given is written fully.
+ * `input` is only read for grad_grid.
+ */
+int drtk_amd_grid_scatter_2d(
+    drtk_dtype_t dtype, const void* input, const void* grid, const int64_t* grid_layout, int64_t N, int64_t C, int64_t H,
+    int64_t W, int64_t output_height, int64_t output_width, int padding_mode, int interpolation_mode, int align_corners,
+    void* out, uint32_t* route_counts, drtk_stream_t stream);
+int drtk_amd_grid_scatter_2d_backward(
+    drtk_dtype_t dtype, const void* grad_out, const void* input, const void* grid, const int64_t* grid_layout, int64_t N,
+    int64_t C, int64_t H, int64_t W, int64_t output_height, int64_t output_width, int padding_mode, int interpolation_mode,
+    int align_corners, void* grad_input, void* grad_grid, const int64_t* grad_grid_layout, drtk_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * screen_space_uv_derivative -- vt_dxdy_img [N,H,W,2,2] = [[du/dx, dv/dx],[du/dy, dv/dy]] per pixel, the
  * Jacobian input of mipmap_grid_sampler_2d; replaces the PyTorch composite
  * drtk/screen_space_uv_derivative.py:15-80 (face_dpdt + 2x interpolate + project_points_grad + inv_ex +
