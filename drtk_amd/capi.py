@@ -148,6 +148,8 @@ EXPORTS = [
     "drtk_amd_mipmap_grid_sampler_2d_backward",
     "drtk_amd_grid_scatter_2d",
     "drtk_amd_grid_scatter_2d_backward",
+    "drtk_amd_msi_forward",
+    "drtk_amd_msi_backward",
     "drtk_amd_screen_space_uv_derivative",
     "drtk_amd_transform_pinhole",
     "drtk_amd_transform_pinhole_backward",
@@ -600,6 +602,43 @@ def grid_scatter_2d_backward(grad_out, input, grid, padding_mode=1, interpolatio
             glayout, _stream(input, stream)),
         "grid_scatter_2d_backward")
     return gi, gg
+
+
+def _msi_args(ray_o, ray_d, texture, sub_step_count, min_inv_r, max_inv_r, stop_thresh):
+    assert ray_o.dtype == th.float32 and ray_d.dtype == th.float32 and ray_o.shape == ray_d.shape and ray_o.shape[1:] == (3,)
+    assert texture.ndim == 4 and texture.shape[1] == 4, texture.shape
+    L, _, H, W = texture.shape
+    return (_i(ray_o.shape[0]), _i(L), _i(H), _i(W), ctypes.c_int(int(sub_step_count)), ctypes.c_double(min_inv_r),
+            ctypes.c_double(max_inv_r), ctypes.c_double(stop_thresh))
+
+
+@_on_tensor_device
+def msi_forward(ray_o, ray_d, texture, sub_step_count=2, min_inv_r=1.0, max_inv_r=0.0, stop_thresh=1e-7, stream=None):
+    """out [N,4] = (r, g, b, log_transmit) of the rays ray_o, ray_d [N,3] (float32) marched through the multi-sphere image
+    texture [L,4,H,W] -- include/drtk_amd.h."""
+    ray_o, ray_d, texture = ray_o.contiguous(), ray_d.contiguous(), texture.contiguous()
+    out = _out(ray_o.shape[0], 4, dtype=texture.dtype, device=texture.device)
+    _check(
+        lib().drtk_amd_msi_forward(
+            ctypes.c_int(_dt(texture)), _p(ray_o), _p(ray_d), _p(texture),
+            *_msi_args(ray_o, ray_d, texture, sub_step_count, min_inv_r, max_inv_r, stop_thresh), _p(out), _stream(texture, stream)),
+        "msi_forward")
+    return out
+
+
+@_on_tensor_device
+def msi_backward(grad_out, out, ray_o, ray_d, texture, sub_step_count=2, min_inv_r=1.0, max_inv_r=0.0, stop_thresh=1e-7, stream=None):
+    """grad_texture [L,4,H,W] from grad_out [N,4] (column 3 is not read) and the forward's `out`."""
+    ray_o, ray_d, texture = ray_o.contiguous(), ray_d.contiguous(), texture.contiguous()
+    grad_out, out = grad_out.contiguous(), out.contiguous()
+    assert grad_out.shape == out.shape == (ray_o.shape[0], 4) and grad_out.dtype == out.dtype == texture.dtype
+    gt = _out(*texture.shape, dtype=texture.dtype, device=texture.device)
+    _check(
+        lib().drtk_amd_msi_backward(
+            ctypes.c_int(_dt(texture)), _p(grad_out), _p(out), _p(ray_o), _p(ray_d), _p(texture),
+            *_msi_args(ray_o, ray_d, texture, sub_step_count, min_inv_r, max_inv_r, stop_thresh), _p(gt), _stream(texture, stream)),
+        "msi_backward")
+    return gt
 
 
 @_on_tensor_device

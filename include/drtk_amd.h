@@ -340,6 +340,36 @@ int drtk_amd_grid_scatter_2d_backward(
     int align_corners, void* grad_input, void* grad_grid, const int64_t* grad_grid_layout, drtk_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * msi -- multi-sphere-image background rendering (NeRF++ style): a stack of L equirectangular RGB-sigma layers on
+ * concentric spheres, one ray per pixel marched through them from the inside out; replaces msi_forward_cuda /
+ * msi_backward_cuda (msi_kernel.cu:411-628).
+ *   ray_o, ray_d [N,3] float32 (whatever the texture's type; ray_d need not be normalised);  texture [L,4,H,W] (r, g, b,
+ *   sigma), contiguous;  out [N,4] = (r, g, b, log_transmit), written fully.
+ *   n = L * sub_step_count spheres with inverse radii from min_inv_r (innermost) towards max_inv_r, sampled bilinearly
+ *   within a layer and by cubic convolution (A = -0.75) across layers, coordinates as grid_sample's align_corners=False
+ *   with border padding; a sample with sigma > 0 adds exp(lt) (1 - exp(-sigma / n)) max(rgb, 0) and lowers lt by
+ *   sigma / n; a ray whose exp(lt) falls below stop_thresh ends with log_transmit = -1000 (csrc/msi.hip has every step).
+ *   sub_step_count >= 1, min_inv_r > max_inv_r, 0 < stop_thresh < 1, N < 2^31, L * 4 * H * W < 2^31.
+ * The texture is read in place, as given: a tap is four loads H * W apart.  No workspace.
+ * ELEMENT TYPES: DRTK_F32 is the tuned path.  With DRTK_F64 the rays are promoted to double on load and the geometry
+ * runs in double too (the reference keeps it in float).
+ * Backward: grad_texture [L,4,H,W] only (the rays get no gradient), zero-filled here and accumulated into; `out` is the
+ * forward's result; grad_out [N,4], of which column 3 is not read.
+ * SIGMA GRADIENT: the reference's expression, sum_ch(max(rgb, 0) g exp(-sigma) T - acc) with T = exp(lt) after the sample
+ * and acc the part of g . out_rgb not yet composited -- not the derivative of the forward, which is
+ * (ref + sum_ch max(rgb, 0) g T (1 - exp(-sigma))) / n ("Multi-sphere background").
+ * REPRODUCIBILITY: the forward is a gather and bit-reproducible; grad_texture is summed with float atomics in varying
+ * order: equal up to rounding from run to run, not bitwise (the reference's is atomic-ordered too).
+ */
+int drtk_amd_msi_forward(
+    drtk_dtype_t dtype, const float* ray_o, const float* ray_d, const void* texture, int64_t N, int64_t L, int64_t H, int64_t W,
+    int sub_step_count, double min_inv_r, double max_inv_r, double stop_thresh, void* out, drtk_stream_t stream);
+int drtk_amd_msi_backward(
+    drtk_dtype_t dtype, const void* grad_out, const void* out, const float* ray_o, const float* ray_d, const void* texture,
+    int64_t N, int64_t L, int64_t H, int64_t W, int sub_step_count, double min_inv_r, double max_inv_r, double stop_thresh,
+    void* grad_texture, drtk_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * screen_space_uv_derivative -- vt_dxdy_img [N,H,W,2,2] = [[du/dx, dv/dx],[du/dy, dv/dy]] per pixel, the
  * Jacobian input of mipmap_grid_sampler_2d; replaces the PyTorch composite
  * drtk/screen_space_uv_derivative.py:15-80 (face_dpdt + 2x interpolate + project_points_grad + inv_ex +
