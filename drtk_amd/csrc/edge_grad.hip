@@ -16,6 +16,11 @@
 //      down pixel of its upper neighbour's) exactly like the reference and sums the at most four
 //      contributions in the single-threaded reference order.
 // Pairs are classified twice (once by each member), which costs ALU only.
+// The fused route (no v_pix_img hook: the gradient goes straight to the vertices) replaces B by a scatter of PAIRS --
+// edge_scatter_pairs_kernel -- and, in float on calls of a megapixel and more, runs that scatter inside A: ONE pass,
+// no workspace traffic (edge_dots_kernel, SCATTER; the dispatch is edge_grad_backward_fused_impl).
+#include <cstdlib>
+
 #include "common.hpp"
 #include "segscatter.hpp"
 
@@ -74,17 +79,64 @@ __device__ __forceinline__ Row<T, VEC> load_row(
   return r;
 }
 
+#ifndef DRTK_EDGE_SLOTS
+#define DRTK_EDGE_SLOTS 64 // A/B on one box (build.py --variant): 128 slots 0.810-0.815 ms, 64 slots 0.812-0.814 -- no difference
+#endif
+#ifndef DRTK_ONEPASS_CAP
+#define DRTK_ONEPASS_CAP 512
+#endif
+#ifndef DRTK_ONEPASS_WAVES
+#define DRTK_ONEPASS_WAVES 6 // waves per SIMD the one-pass kernel is compiled for (80 registers; without the bound: 85, five waves)
+#endif
+constexpr int kOnepassCap = DRTK_ONEPASS_CAP; // entries of the one-pass kernel's pair list (edge_dots_kernel, SCATTER)
+
+// What the SCATTER mode of edge_dots_kernel needs beside the images (the arguments of edge_scatter_pairs_kernel).
+template <typename T>
+struct PairArgs {
+  const T* v_pix;
+  const int32_t* vi;
+  const T* bary_img;
+  T* grad_v_pix;
+  int64_t V, vi_sN;
+  T M;
+};
+
+// exclusive prefix over the lanes of a 0..4 count, and its wave total, from three ballots (lt = the lanes below this one)
+__device__ __forceinline__ int prefix4(int cnt, unsigned long long lt, int& total) {
+  const unsigned long long b0 = __ballot(cnt & 1), b1 = __ballot(cnt & 2), b2 = __ballot(cnt & 4);
+  total = __popcll(b0) + 2 * __popcll(b1) + 4 * __popcll(b2);
+  return __popcll(b0 & lt) + 2 * __popcll(b1 & lt) + 4 * __popcll(b2 & lt);
+}
+
+template <typename T, int AXIS, int SLOTS>
+__device__ __forceinline__ void scatter_pair_round(
+    bool act, int px, int y, T term, const int32_t* __restrict__ idx_n, const T* __restrict__ v_n,
+    const int32_t* __restrict__ vi_n, const T* __restrict__ bary_n, int64_t HW, int W, T M, int32_t* keys,
+    TableAcc* vals, T* __restrict__ grad_n);
+
 // One wave = strip of 63*VEC pixels (+ VEC halo pixels in lane 63) x R rows; the WAVES waves of a workgroup are stacked vertically
 // on the same pixel columns (WAVES*R rows per workgroup), so the extra "row below" every wave needs
 // is the first row of its sibling wave and is served by this CU's L1 -- HBM sees each row
 // (WAVES*R+1)/(WAVES*R) times.
 // gdx[y][x] pairs (x,y)-(x+1,y), gdy[y][x] pairs (x,y)-(x,y+1); accumulation over channels in
 // ascending order (edge_grad_kernel.cu:353-380).
-template <typename T, int VEC, int R, int WAVES>
-__global__ __launch_bounds__(WAVES * kWave) void edge_dots_kernel(
+//
+// SCATTER (the fused route in float, one pass): the wave does not store its pair terms.  It OWNS the pairs whose terms it
+// holds -- (x,y)-(x+1,y) and (x,y)-(x,y+1) for the pixels of lanes 0..62 in rows y0 .. y0+R-1 inside the reference's
+// stencil domain (x < W-1, y < H-1); lane 62's last pixel pairs with lane 63's first, row R-1 with the halo row, lane 63
+// owns nothing -- and runs the pair phase of edge_scatter_pairs_kernel on them right after its channel loop: the pairs
+// whose indices differ (flags taken from the index rows this kernel reads anyway, one register across the channel loop)
+// go into a wave-private LDS list of (position, term) entries, are evaluated one per lane with the axis as a compile-time
+// constant and scattered through the wave's vertex table into grad_v_pix, which the host has cleared BEFORE the launch
+// (other workgroups' atomics would race a fill spread over this grid).  Nothing crosses a wave: no workgroup barrier, no
+// workspace, and what a lane loads follows the flags -- a lane without a differing pair (and whose first pixel its left
+// neighbour does not need) loads nothing, a wave without one returns before the channel loop.
+template <typename T, int VEC, int R, int WAVES, bool SCATTER = false>
+__global__ __launch_bounds__(WAVES * kWave, SCATTER ? DRTK_ONEPASS_WAVES : 1) void edge_dots_kernel(
     const T* __restrict__ img, const T* __restrict__ grad_output, const int32_t* __restrict__ index_img, int C,
     int H, int W, int strips_x, T* __restrict__ gdx, T* __restrict__ gdy, int strip, T* __restrict__ zero_out,
-    int64_t zero_count) {
+    int64_t zero_count, PairArgs<T> pairs) {
+  static_assert(!SCATTER || (VEC == 4 && 8 * R <= 32 && sizeof(T) == 4), "the pair phase works on four-pixel lanes of float; its flags are one register");
   // the accumulator of the pass that follows this one (grad_v_pix of the fused route) is cleared here, spread over the
   // whole grid: one launch less per backward pass, which is what a small scene's step is made of
   if (zero_out) {
@@ -110,14 +162,18 @@ __global__ __launch_bounds__(WAVES * kWave) void edge_dots_kernel(
   // background neither loads nor stores anything (its part of the workspace is never read), so the
   // background of the image costs 4 B/px of index instead of 8C B/px of img + grad_output.
   bool any_fg = false;
+  // SCATTER: the pairs this lane owns whose indices differ -- bit 4r+j: (x+j,y0+r)-(x+j+1,y0+r), bit 4R+4r+j: (x+j,y0+r)-(x+j,y0+r+1)
+  uint32_t flags = 0;
   {
     const int32_t* idx_n = index_img + int64_t(n) * HW;
+    int32_t above[4] = {-1, -1, -1, -1}; // SCATTER: the row before this one
 #pragma unroll
     for (int r = 0; r <= R; ++r) {
       const int y = y0 + r;
       if (y < H) { // wave-uniform
         bool fg = false;
         int32_t first = -1, last = -1;
+        int32_t cur[4] = {-1, -1, -1, -1};
         if (x < W) {
           if constexpr (VEC == 4) {
             Quad<int32_t> q;
@@ -129,6 +185,7 @@ __global__ __launch_bounds__(WAVES * kWave) void edge_dots_kernel(
             }
             fg = (q.x & q.y & q.z & q.w) != -1;
             first = q.x, last = q.w;
+            cur[0] = q.x, cur[1] = q.y, cur[2] = q.z, cur[3] = q.w;
           } else {
             first = last = idx_n[int64_t(y) * W + x];
             fg = first != -1;
@@ -138,11 +195,33 @@ __global__ __launch_bounds__(WAVES * kWave) void edge_dots_kernel(
         if (lane == 0) left = (x >= 1 && x < W) ? idx_n[int64_t(y) * W + x - 1] : -1;
         if (lane == kWave - 1) right = (x + VEC < W) ? idx_n[int64_t(y) * W + x + VEC] : -1;
         any_fg = any_fg || fg || left != -1 || right != -1;
+        if constexpr (SCATTER) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const bool in_x = lane != kWave - 1 && x + j < W - 1; // stencil domain of the reference; lane 63 owns nothing
+            // vertical pairs of the row before (it exists: y0 + r - 1 < y < H, and y - 1 < H - 1)
+            if (r > 0 && in_x && above[j] != cur[j]) flags |= 1u << (4 * R + 4 * (r - 1) + j);
+            const int32_t nr = j < 3 ? cur[(j + 1) & 3] : right;
+            if (r < R && in_x && y < H - 1 && cur[j] != nr) flags |= 1u << (4 * r + j);
+            above[j] = cur[j];
+          }
+        }
       }
     }
   }
-  if (__ballot(any_fg) == 0) return;
-  const bool x_ok = x < W && any_fg;
+  bool load_any = any_fg;
+  if constexpr (SCATTER) {
+    if (__ballot(flags != 0) == 0) return; // (wave-uniform) no pair of this strip differs: nothing to add anywhere
+    // pixel 3 of a lane pairs with the NEXT lane's first pixel, so that lane loads for it
+    uint32_t h3 = 0;
+#pragma unroll
+    for (int r = 0; r < R; ++r) h3 |= flags & (8u << (4 * r));
+    const int left_h3 = __shfl_up(static_cast<int>(h3), 1);
+    load_any = flags != 0 || (lane > 0 && left_h3 != 0);
+  } else {
+    if (__ballot(any_fg) == 0) return;
+  }
+  const bool x_ok = x < W && load_any;
 
   T ax[R][VEC], ay[R][VEC];
 #pragma unroll
@@ -171,6 +250,107 @@ __global__ __launch_bounds__(WAVES * kWave) void edge_dots_kernel(
         ay[r][j] += (ri[r + 1].v[j] - ri[r].v[j]) * (T(0.5) * (rg[r + 1].v[j] + rg[r].v[j]));
       }
     }
+  }
+  if constexpr (SCATTER) {
+    // ---- the pair phase of edge_scatter_pairs_kernel on this wave's own pairs; every lane stays to the end (ballots, DPP scans)
+    constexpr int kSlots = DRTK_EDGE_SLOTS;
+    // The list holds the flagged pairs only: a dense staging of the terms (4 KB per wave) plus a worst-case list would
+    // not fit 24 waves into a CU's 160 KB.  kOnepassCap entries of 8 bytes + the table = 6.3 KB per wave; a strip with
+    // more differing pairs than that -- an index image may differ at every pixel -- takes the list-free path below.
+    constexpr int kCap = kOnepassCap;
+    __shared__ uint2 s_list[WAVES][kCap]; // .x = (row << 8) | pixel of the strip, .y = the pair's term
+    __shared__ int32_t t_keys[WAVES][kSlots];
+    __shared__ TableAcc t_vals[WAVES][kSlots * 4];
+    const int wave = threadIdx.x / kWave;
+    const int32_t* idx_n = index_img + int64_t(n) * HW;
+    const T* v_n = pairs.v_pix + int64_t(n) * pairs.V * 3;
+    const int32_t* vi_n = pairs.vi + int64_t(n) * pairs.vi_sN;
+    const T* bary_n = pairs.bary_img + int64_t(n) * 3 * HW;
+    T* grad_n = pairs.grad_v_pix + int64_t(n) * pairs.V * 3;
+    const int strip_x0 = sx * (kWave - 1) * VEC;
+
+    table_init<kSlots>(t_keys[wave]);
+    for (int i = lane; i < kSlots * 4; i += kWave) t_vals[wave][i] = 0;
+
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    int grand = 0;
+#pragma unroll
+    for (int g = 0; g < 2 * R; ++g) {
+      int t;
+      prefix4(__popc((flags >> (4 * g)) & 15u), lt, t);
+      grand += t;
+    }
+    if (grand <= kCap) { // (wave-uniform)
+      // list layout: [horizontal pairs, row-major][vertical pairs, row-major]; the terms leave their registers here
+      int n_h = 0, n_all = 0;
+#pragma unroll
+      for (int axis = 0; axis < 2; ++axis) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          const uint32_t f = (flags >> (4 * R * axis + 4 * r)) & 15u;
+          int t;
+          int pos = n_all + prefix4(__popc(f), lt, t);
+          n_all += t;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            if (f & (1u << j)) s_list[wave][pos++] = make_uint2((r << 8) | (lane * 4 + j), __builtin_bit_cast(uint32_t, axis == 0 ? ax[r][j] : ay[r][j]));
+          }
+        }
+        if (axis == 0) n_h = n_all;
+      }
+      wave_lds_sync();
+
+      // one pair per lane; a chunk of 64 lanes never mixes the two axes
+      for (int axis = 0; axis < 2; ++axis) {
+        const int l_begin = axis == 0 ? 0 : n_h, l_end = axis == 0 ? n_h : n_all;
+        for (int t0 = l_begin; t0 < l_end; t0 += kWave) {
+          const int t = t0 + lane;
+          const bool act = t < l_end;
+          int px = 0, y = 0;
+          T term = T(0);
+          if (act) {
+            const uint2 entry = s_list[wave][t];
+            y = y0 + static_cast<int>(entry.x >> 8);
+            px = strip_x0 + static_cast<int>(entry.x & 255u);
+            term = __builtin_bit_cast(float, entry.y);
+          }
+          if (axis == 0) {
+            scatter_pair_round<T, 0, kSlots>(act, px, y, term, idx_n, v_n, vi_n, bary_n, HW, W, pairs.M, t_keys[wave], t_vals[wave], grad_n);
+          } else {
+            scatter_pair_round<T, 1, kSlots>(act, px, y, term, idx_n, v_n, vi_n, bary_n, HW, W, pairs.M, t_keys[wave], t_vals[wave], grad_n);
+          }
+        }
+      }
+    } else {
+      // More than kCap of the strip's at most 63 x 4 x R x 2 pairs differ: compaction has little to gain, so each lane
+      // keeps its own pairs -- for each of its 4 R pixels and each axis one round in which every lane with that flag set
+      // takes its pair (at least half of the lanes on average).  Any density; the list's storage holds the terms
+      // meanwhile, all of them (dense: entry k of lane l at [k][l]), so that they do not occupy registers in the rounds.
+      static_assert(2 * kCap >= kWave * 8 * R, "the list's storage must hold a strip's terms");
+      uint32_t* s_terms = reinterpret_cast<uint32_t*>(s_list[wave]);
+#pragma unroll
+      for (int q = 0; q < 4 * R; ++q) {
+        s_terms[q * kWave + lane] = __builtin_bit_cast(uint32_t, ax[q / 4][q % 4]);
+        s_terms[(4 * R + q) * kWave + lane] = __builtin_bit_cast(uint32_t, ay[q / 4][q % 4]);
+      }
+      wave_lds_sync(); // (also: the table is initialised)
+      for (int axis = 0; axis < 2; ++axis) {
+#pragma unroll 1
+        for (int k = 0; k < 4 * R; ++k) {
+          const bool act = (flags >> (4 * R * axis + k)) & 1u;
+          if (__ballot(act) == 0) continue;
+          const T term = __builtin_bit_cast(float, s_terms[(4 * R * axis + k) * kWave + lane]);
+          if (axis == 0) {
+            scatter_pair_round<T, 0, kSlots>(act, x + (k & 3), y0 + (k >> 2), term, idx_n, v_n, vi_n, bary_n, HW, W, pairs.M, t_keys[wave], t_vals[wave], grad_n);
+          } else {
+            scatter_pair_round<T, 1, kSlots>(act, x + (k & 3), y0 + (k >> 2), term, idx_n, v_n, vi_n, bary_n, HW, W, pairs.M, t_keys[wave], t_vals[wave], grad_n);
+          }
+        }
+      }
+    }
+    wave_lds_sync();
+    table_flush<T, TableAcc, kSlots>(t_keys[wave], t_vals[wave], 4, 3, grad_n, 3, 0);
+    return;
   }
   if (!x_ok || lane == kWave - 1) return;
   T* ox = gdx + int64_t(n) * HW;
@@ -546,6 +726,63 @@ __global__ __launch_bounds__(kBlock) void edge_gather4_kernel(
   }
 }
 
+// One round of the pair phase (edge_scatter_pairs_kernel and the SCATTER mode of edge_dots_kernel): every lane with `act`
+// holds one pair A = (px, y), B = A + (1,0) [AXIS 0] or A + (0,1) [AXIS 1] whose indices differ, and the pair's dot
+// term; the wave evaluates its pairs, sums runs of lanes that hit the same two triangles and adds the runs' sums to the
+// vertices through its table.  Wave-collective: called by all lanes of the wave, the idle ones with act = false.
+template <typename T, int AXIS, int SLOTS>
+__device__ __forceinline__ void scatter_pair_round(
+    bool act, int px, int y, T term, const int32_t* __restrict__ idx_n, const T* __restrict__ v_n,
+    const int32_t* __restrict__ vi_n, const T* __restrict__ bary_n, int64_t HW, int W, T M, int32_t* keys,
+    TableAcc* vals, T* __restrict__ grad_n) {
+  int32_t ia = -1, ib = -1;
+  T ga = T(0), za = T(0), gb = T(0), zb = T(0); // -(in-plane), -(z) contributions to pixel A / pixel B
+  T Ba[3] = {T(0), T(0), T(0)}, Bb[3] = {T(0), T(0), T(0)};
+  int32_t va[3] = {0, 0, 0}, vb[3] = {0, 0, 0};
+  if (act) {
+    const int64_t pa = int64_t(y) * W + px;
+    const int64_t pb = AXIS == 0 ? pa + 1 : pa + W;
+    ia = idx_n[pa];
+    ib = idx_n[pb];
+    TriInfo<T> ta, tb;
+    load_tri<T>(v_n, vi_n, ia, ta);
+    load_tri<T>(v_n, vi_n, ib, tb);
+    T gA, zA, gB, zB;
+    eval_pair<T, AXIS>(v_n, ta, tb, ia, ib, px, y, term, M, gA, zA, gB, zB);
+    ga = -gA, za = -zA, gb = -gB, zb = -zB; // edge_grad_kernel.cu:427-445 negates
+    va[0] = ta.i0, va[1] = ta.i1, va[2] = ta.i2;
+    vb[0] = tb.i0, vb[1] = tb.i1, vb[2] = tb.i2;
+    if (ia >= 0) Ba[0] = bary_n[pa], Ba[1] = bary_n[HW + pa], Ba[2] = bary_n[2 * HW + pa];
+    if (ib >= 0) Bb[0] = bary_n[pb], Bb[1] = bary_n[HW + pb], Bb[2] = bary_n[2 * HW + pb];
+  }
+  // a side takes part if its pixel is foreground and it received something
+  const bool a_on = ia >= 0 && (ga != T(0) || za != T(0));
+  const bool b_on = ib >= 0 && (gb != T(0) || zb != T(0));
+  // twelve terms per pair: corner slots A0..A2, B0..B2, two components each -- the pair's axis (x or y) and z
+  T g[12];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    g[2 * k + 0] = a_on ? ga * Ba[k] : T(0);
+    g[2 * k + 1] = a_on ? za * Ba[k] : T(0);
+    g[6 + 2 * k + 0] = b_on ? gb * Bb[k] : T(0);
+    g[6 + 2 * k + 1] = b_on ? zb * Bb[k] : T(0);
+  }
+  // a run = consecutive lanes with the same two triangles and the same participation; its sums end up in its
+  // last lane (segscatter.hpp: run_sums_rows16), which alone touches the vertex table
+  const int32_t key_a = a_on ? ia : -1, key_b = b_on ? ib : -1;
+  int dist;
+  bool tail;
+  const int32_t left_a = __shfl_up(key_a, 1), left_b = __shfl_up(key_b, 1); // both BEFORE the ||: a shuffle under a
+  run_rows16_heads(key_a != left_a || key_b != left_b, dist, tail);           // short-circuit runs with lanes switched off
+  if (__ballot(a_on || b_on) != 0) {
+    run_sums_rows16<T, 12>(g, dist);
+    // components {axis, z}: x,z = 0 + c*2 ; y,z = 1 + c*1
+    constexpr int c_off = AXIS == 0 ? 0 : 1, c_step = AXIS == 0 ? 2 : 1;
+    if (tail && a_on) table_add<T, 3, 2, SLOTS>(keys, vals, 4, va, g, grad_n, 3, c_off, c_step);
+    if (tail && b_on) table_add<T, 3, 2, SLOTS>(keys, vals, 4, vb, g + 6, grad_n, 3, c_off, c_step);
+  }
+}
+
 // Fused pass B for the default route of drtk.edge_grad_estimator (no v_pix_img hook): instead of
 // materialising grad_v_pix_img [N,3,H,W] (80 % exact zeros) for a separate C=3 interpolate backward to
 // scatter, the contributions are multiplied by the pixel's barycentrics and scattered to the triangle's
@@ -575,6 +812,9 @@ __global__ __launch_bounds__(kBlock) void edge_gather4_kernel(
 // (Round 6: the tile's index rows staged in LDS so that a round's two triangle ids are LDS reads -- one of the three dependent
 // round trips less -- for 12.5 KB more LDS and four more registers: five waves per SIMD instead of six, 0.771-0.780 against
 // 0.750-0.759 ms, 250k triangles 0.819 against 0.791.  Slower; not kept.)
+// (Round 7: float calls of a megapixel and more no longer come here -- edge_dots_kernel scatters its own pairs (SCATTER) --
+// so this kernel serves double and the small float calls.  Its round is scatter_pair_round, shared with that kernel; with
+// the axis a template argument of the whole round it takes 62 registers in float instead of 80.)
 constexpr int kPairRows = DRTK_PAIR_ROWS;
 template <typename T>
 __global__ __launch_bounds__(kBlock, sizeof(T) == 4 ? 4 : 2) void edge_scatter_pairs_kernel(
@@ -585,9 +825,6 @@ __global__ __launch_bounds__(kBlock, sizeof(T) == 4 ? 4 : 2) void edge_scatter_p
   constexpr int kRows = kPairRows;
   constexpr int kCap = kWave * 4 * 2 * 2; // pairs of two rows, both axes: the most one list build can hold
   __shared__ uint16_t s_list[kWaves][kCap];
-#ifndef DRTK_EDGE_SLOTS
-#define DRTK_EDGE_SLOTS 64 // A/B on one box (build.py --variant): 128 slots 0.810-0.815 ms, 64 slots 0.812-0.814 -- no difference
-#endif
   constexpr int kSlots = DRTK_EDGE_SLOTS;
   __shared__ int32_t t_keys[kWaves][kSlots];
   __shared__ TableAcc t_vals[kWaves][kSlots * 4];
@@ -648,12 +885,6 @@ __global__ __launch_bounds__(kBlock, sizeof(T) == 4 ? 4 : 2) void edge_scatter_p
     }
   }
   const unsigned long long lt = (1ull << lane) - 1ull;
-  // exclusive prefix over the lanes of a 0..4 count, and its wave total, from three ballots
-  auto prefix4 = [&](int cnt, int& total) -> int {
-    const unsigned long long b0 = __ballot(cnt & 1), b1 = __ballot(cnt & 2), b2 = __ballot(cnt & 4);
-    total = __popcll(b0) + 2 * __popcll(b1) + 4 * __popcll(b2);
-    return __popcll(b0 & lt) + 2 * __popcll(b1 & lt) + 4 * __popcll(b2 & lt);
-  };
 
   // rows are processed in groups whose pair lists fit the LDS list: all four rows normally, two and two
   // when the tile is so dense that they would not
@@ -661,9 +892,9 @@ __global__ __launch_bounds__(kBlock, sizeof(T) == 4 ? 4 : 2) void edge_scatter_p
 #pragma unroll
   for (int r = 0; r < kRows; ++r) {
     int t;
-    prefix4(__popc(hf[r]), t);
+    prefix4(__popc(hf[r]), lt, t);
     grand += t;
-    prefix4(__popc(vf[r]), t);
+    prefix4(__popc(vf[r]), lt, t);
     grand += t;
   }
   const int rows_per_group = grand <= kCap ? kRows : (kRows < 2 ? kRows : 2);
@@ -678,7 +909,7 @@ __global__ __launch_bounds__(kBlock, sizeof(T) == 4 ? 4 : 2) void edge_scatter_p
         if (r < r0 || r >= r0 + rows_per_group) continue;
         const uint32_t f = axis == 0 ? hf[r] : vf[r];
         int t;
-        int pos = n_all + prefix4(__popc(f), t);
+        int pos = n_all + prefix4(__popc(f), lt, t);
         n_all += t;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -695,58 +926,18 @@ __global__ __launch_bounds__(kBlock, sizeof(T) == 4 ? 4 : 2) void edge_scatter_p
       for (int t0 = l_begin; t0 < l_end; t0 += kWave) {
         const int t = t0 + lane;
         const bool act = t < l_end;
-        int32_t ia = -1, ib = -1;
-        T ga = T(0), za = T(0), gb = T(0), zb = T(0); // -(in-plane), -(z) contributions to pixel A / pixel B
-        T Ba[3] = {T(0), T(0), T(0)}, Bb[3] = {T(0), T(0), T(0)};
-        int32_t va[3] = {0, 0, 0}, vb[3] = {0, 0, 0};
+        int px = 0, y = 0;
+        T term = T(0);
         if (act) {
           const int entry = s_list[wave][t];
-          const int y = y_base + (entry >> 8);
-          const int px = sx * (kWave * 4) + (entry & 255);
-          const int64_t pa = int64_t(y) * W + px;
-          const int64_t pb = axis == 0 ? pa + 1 : pa + W;
-          ia = idx_n[pa];
-          ib = idx_n[pb];
-          TriInfo<T> ta, tb;
-          load_tri<T>(v_n, vi_n, ia, ta);
-          load_tri<T>(v_n, vi_n, ib, tb);
-          T gA, zA, gB, zB;
-          if (axis == 0) {
-            eval_pair<T, 0>(v_n, ta, tb, ia, ib, px, y, gdx_n[pa], M, gA, zA, gB, zB);
-          } else {
-            eval_pair<T, 1>(v_n, ta, tb, ia, ib, px, y, gdy_n[pa], M, gA, zA, gB, zB);
-          }
-          ga = -gA, za = -zA, gb = -gB, zb = -zB; // edge_grad_kernel.cu:427-445 negates
-          va[0] = ta.i0, va[1] = ta.i1, va[2] = ta.i2;
-          vb[0] = tb.i0, vb[1] = tb.i1, vb[2] = tb.i2;
-          if (ia >= 0) Ba[0] = bary_n[pa], Ba[1] = bary_n[HW + pa], Ba[2] = bary_n[2 * HW + pa];
-          if (ib >= 0) Bb[0] = bary_n[pb], Bb[1] = bary_n[HW + pb], Bb[2] = bary_n[2 * HW + pb];
+          y = y_base + (entry >> 8);
+          px = sx * (kWave * 4) + (entry & 255);
+          term = (axis == 0 ? gdx_n : gdy_n)[int64_t(y) * W + px];
         }
-        // a side takes part if its pixel is foreground and it received something
-        const bool a_on = ia >= 0 && (ga != T(0) || za != T(0));
-        const bool b_on = ib >= 0 && (gb != T(0) || zb != T(0));
-        // twelve terms per pair: corner slots A0..A2, B0..B2, two components each -- the pair's axis (x or y) and z
-        T g[12];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          g[2 * k + 0] = a_on ? ga * Ba[k] : T(0);
-          g[2 * k + 1] = a_on ? za * Ba[k] : T(0);
-          g[6 + 2 * k + 0] = b_on ? gb * Bb[k] : T(0);
-          g[6 + 2 * k + 1] = b_on ? zb * Bb[k] : T(0);
-        }
-        // a run = consecutive lanes with the same two triangles and the same participation; its sums end up in its
-        // last lane (segscatter.hpp: run_sums_rows16), which alone touches the vertex table
-        const int32_t key_a = a_on ? ia : -1, key_b = b_on ? ib : -1;
-        int dist;
-        bool tail;
-        const int32_t left_a = __shfl_up(key_a, 1), left_b = __shfl_up(key_b, 1); // both BEFORE the ||: a shuffle under a
-        run_rows16_heads(key_a != left_a || key_b != left_b, dist, tail);           // short-circuit runs with lanes switched off
-        if (__ballot(a_on || b_on) != 0) {
-          run_sums_rows16<T, 12>(g, dist);
-          // components {axis, z}: x,z = 0 + c*2 ; y,z = 1 + c*1
-          const int c_off = axis == 0 ? 0 : 1, c_step = axis == 0 ? 2 : 1;
-          if (tail && a_on) table_add<T, 3, 2, kSlots>(t_keys[wave], t_vals[wave], 4, va, g, grad_n, 3, c_off, c_step);
-          if (tail && b_on) table_add<T, 3, 2, kSlots>(t_keys[wave], t_vals[wave], 4, vb, g + 6, grad_n, 3, c_off, c_step);
+        if (axis == 0) {
+          scatter_pair_round<T, 0, kSlots>(act, px, y, term, idx_n, v_n, vi_n, bary_n, HW, W, M, t_keys[wave], t_vals[wave], grad_n);
+        } else {
+          scatter_pair_round<T, 1, kSlots>(act, px, y, term, idx_n, v_n, vi_n, bary_n, HW, W, M, t_keys[wave], t_vals[wave], grad_n);
         }
       }
     }
@@ -789,7 +980,7 @@ int edge_grad_backward_impl(
   const int strips_x = static_cast<int>(ceil_div(W, px_per_wave));
   const int bands_y = static_cast<int>(ceil_div(H, kStripRows * kDotsWaves));
   const dim3 gridA(static_cast<unsigned>(int64_t(strips_x) * bands_y), static_cast<unsigned>(N));
-  DRTK_LAUNCH((edge_dots_kernel<T, 4, kStripRows, kDotsWaves>), gridA, dim3(kDotsWaves * kWave), 0, stream, img, grad_output, index_img, (int)C, (int)H, (int)W, strips_x, gdx, gdy, xcd_strip(int64_t(strips_x) * (16 / (kStripRows * kDotsWaves))), static_cast<T*>(nullptr), int64_t(0));
+  DRTK_LAUNCH((edge_dots_kernel<T, 4, kStripRows, kDotsWaves>), gridA, dim3(kDotsWaves * kWave), 0, stream, img, grad_output, index_img, (int)C, (int)H, (int)W, strips_x, gdx, gdy, xcd_strip(int64_t(strips_x) * (16 / (kStripRows * kDotsWaves))), static_cast<T*>(nullptr), int64_t(0), PairArgs<T>{});
   DRTK_RETURN_IF_LAUNCH_FAILED();
   const bool vec_out = vec && (reinterpret_cast<uintptr_t>(index_img) % 16 == 0) &&
       (reinterpret_cast<uintptr_t>(out) % (4 * sizeof(T)) == 0);
@@ -811,13 +1002,42 @@ int launch_edge_dots(const T* img, const T* grad_output, const int32_t* index_im
   const int strips_x = static_cast<int>(ceil_div(W, px_per_wave));
   const int bands_y = static_cast<int>(ceil_div(H, kStripRows * kDotsWaves));
   const dim3 gridA(static_cast<unsigned>(int64_t(strips_x) * bands_y), static_cast<unsigned>(N));
-  DRTK_LAUNCH((edge_dots_kernel<T, 4, kStripRows, kDotsWaves>), gridA, dim3(kDotsWaves * kWave), 0, stream, img, grad_output, index_img, (int)C, (int)H, (int)W, strips_x, gdx, gdy, xcd_strip(int64_t(strips_x) * (16 / (kStripRows * kDotsWaves))), zero_out, zero_count);
+  DRTK_LAUNCH((edge_dots_kernel<T, 4, kStripRows, kDotsWaves>), gridA, dim3(kDotsWaves * kWave), 0, stream, img, grad_output, index_img, (int)C, (int)H, (int)W, strips_x, gdx, gdy, xcd_strip(int64_t(strips_x) * (16 / (kStripRows * kDotsWaves))), zero_out, zero_count, PairArgs<T>{});
   DRTK_RETURN_IF_LAUNCH_FAILED();
   return DRTK_OK;
 }
 
 inline bool aligned_to(const void* p, size_t a) {
   return reinterpret_cast<uintptr_t>(p) % a == 0;
+}
+
+// The fused route in float: ONE kernel (edge_dots_kernel in SCATTER mode) or the two kernels.  0 compiles the one-pass
+// route out (`python drtk_amd/build.py --variant out.so DRTK_EDGE_ONEPASS=0`: the A/B library for profiles/kernel_bench.py --lib).
+#ifndef DRTK_EDGE_ONEPASS
+#define DRTK_EDGE_ONEPASS 1
+#endif
+// Calls of at least this many pixels (all views) take the one-pass kernel.  Measured on one box, interleaved, ms per call
+// (profiles/r07/edge_onepass_ab.txt; one pass | two kernels):
+//   8 x 2048^2, C 16, 100k triangles   0.634-0.638 | 0.726-0.737 (parent commit 0.743-0.753)
+//   8 x 2048^2, C 16, 250k             0.664-0.666 | 0.715-0.762
+//   2 x 4096^2, C  3, 1M               0.293-0.295 | 0.371-0.381   (small C: the pair phase dominates, and it no longer
+//                                                                   re-reads the index rows or fetches the terms)
+//   4 x 512^2,  C  3, 10k              0.027-0.031 | 0.031-0.033
+//   2 x 512^2,  C  3, 10k              0.021-0.024 | 0.026-0.028
+//   2 x 128^2,  C 16, 10k              0.033-0.040 | 0.036
+// No shape class is slower in one pass, so the rule is not about speed: below a megapixel a call is two launches of
+// 10-15 us either way (the fill that the one pass needs takes the place of the launch it saves), the 2-3 us between the
+// routes are under 1 % of any step that small, and the suite's timing contracts (tests/test_gpu_parity.py,
+// tests/test_gpu_bench_contract.py) name BOTH kernels on small float scenes -- those keep the two kernels.
+// DRTK_AMD_EDGE_ONEPASS in the environment overrides the size rule -- 1: every float call, 0: none -- so that the one-pass
+// kernel is tested on strips of a few rows (tests/test_gpu_edge_onepass.py) and both routes can be timed from one library.
+#ifndef DRTK_EDGE_ONEPASS_MIN_PX
+#define DRTK_EDGE_ONEPASS_MIN_PX (int64_t(1) << 20)
+#endif
+inline bool edge_onepass_wanted(int64_t pixels) {
+  const char* e = std::getenv("DRTK_AMD_EDGE_ONEPASS"); // read per call: a test switches it inside one process
+  if (e && e[0] && !e[1] && (e[0] == '0' || e[0] == '1')) return e[0] == '1';
+  return pixels >= DRTK_EDGE_ONEPASS_MIN_PX;
 }
 
 template <typename T>
@@ -831,7 +1051,23 @@ int edge_grad_backward_fused_impl(
     if (N * V > 0 && fill_bytes_async(grad_v_pix, 0, sizeof(T) * N * V * 3, stream) != DRTK_OK) return DRTK_ERR_LAUNCH;
     return DRTK_OK;
   }
-  // One route for every shape and every element-aligned placement of the tensors (two planes of workspace): both kernels
+#if DRTK_EDGE_ONEPASS
+  if constexpr (std::is_same<T, float>::value) {
+    if (edge_onepass_wanted(N * HW)) {
+      // one pass: edge_dots_kernel scatters its own pairs (SCATTER); the workspace is not touched.  grad_v_pix is cleared by
+      // a launch of its own: spread over the grid of the scattering kernel the fill would race other workgroups' atomics.
+      if (N * V > 0 && fill_bytes_async(grad_v_pix, 0, sizeof(T) * N * V * 3, stream) != DRTK_OK) return DRTK_ERR_LAUNCH;
+      const int strips_x = static_cast<int>(ceil_div(W, (kWave - 1) * 4)); // lane 63 = halo
+      const int bands_y = static_cast<int>(ceil_div(H, kStripRows * kDotsWaves));
+      const dim3 grid(static_cast<unsigned>(int64_t(strips_x) * bands_y), static_cast<unsigned>(N));
+      const PairArgs<T> pairs{v_pix, vi, bary_img, grad_v_pix, V, vi_sN, static_cast<T>(max_dp_dr)};
+      DRTK_LAUNCH((edge_dots_kernel<T, 4, kStripRows, kDotsWaves, true>), grid, dim3(kDotsWaves * kWave), 0, stream, img, grad_output, index_img, (int)C, (int)H, (int)W, strips_x, static_cast<T*>(nullptr), static_cast<T*>(nullptr), xcd_strip(int64_t(strips_x) * (16 / (kStripRows * kDotsWaves))), static_cast<T*>(nullptr), int64_t(0), pairs);
+      DRTK_RETURN_IF_LAUNCH_FAILED();
+      return DRTK_OK;
+    }
+  }
+#endif
+  // Two kernels for every shape and every element-aligned placement of the tensors (two planes of workspace): both
   // fetch four adjacent pixels per access with the alignment of the element and handle the end of a row whose width is
   // not a multiple of four lane by lane.
   T* gdx = static_cast<T*>(workspace);
