@@ -1,9 +1,19 @@
 """drtk_amd -- MI355X-native differentiable rasterization hot path
 (rasterize -> render -> interpolate -> edge_grad), drop-in for the `drtk.*` functions of
 facebookresearch/DRTK on PyTorch-ROCm, plus the mesh geometry of `drtk.utils` (vertex normals,
-face info, UV Jacobians, binormals), `grid_scatter` and the `msi` background.  Kernels: hand-written HIP for gfx950 in
+face info, UV Jacobians, binormals), `grid_scatter`, the `msi` background and the `filter2d` resampling filters.  Kernels: hand-written HIP for gfx950 in
 `drtk_amd/csrc`, C ABI in `include/drtk_amd.h`."""
 from drtk_amd.edge_grad_estimator import edge_grad_estimator  # noqa: F401
+from drtk_amd.filter2d import (  # noqa: F401
+    FilterOptions,
+    FilterType,
+    downsample,
+    filter,
+    low_pass_filter,
+    make_resampling_kernel,
+    resample_filter,
+    upsample,
+)
 from drtk_amd.geometry import (  # noqa: F401
     face_attribute_to_vert,
     face_dpdt,
@@ -41,9 +51,9 @@ __version__ = "0.1.0"
 # reference as its setup.py builds it) and `rasterize_layers` / `rasterize_layers_with_depth` (the K nearest triangles per
 # pixel, for front-to-back compositing) are this package's additions.  The mesh geometry of drtk.utils (face_info,
 # vert_normals, face_attribute_to_vert, face_dpdt, vert_binormals) is exported here too, and so is `grid_scatter` (the
-# splatting counterpart of grid_sample) and `msi` (the multi-sphere-image background); the `drtk` drop-in package does not
-# lift these two yet -- INTEGRATION.md.  Not provided: filter2d and the pure-PyTorch `*_ref` models (out of
-# scope).
+# splatting counterpart of grid_sample), `msi` (the multi-sphere-image background) and the eight names of `filter2d` (fused
+# alias-free up/down-sampling and low-pass filtering); the `drtk` drop-in package does not lift these three yet --
+# INTEGRATION.md.  Not provided: the pure-PyTorch `*_ref` models (out of scope).
 __all__ = [
     "rasterize",
     "rasterize_with_depth",
@@ -58,6 +68,14 @@ __all__ = [
     "mipmap_grid_sample",
     "grid_scatter",
     "msi",
+    "FilterType",
+    "FilterOptions",
+    "resample_filter",
+    "filter",
+    "low_pass_filter",
+    "downsample",
+    "upsample",
+    "make_resampling_kernel",
     "screen_space_uv_derivative",
     "transform",
     "transform_with_v_cam",

@@ -15,7 +15,7 @@ from drtk_amd.utils import native_library_paths
 
 _lib = None
 
-DRTK_F32, DRTK_F64 = 0, 1
+DRTK_F32, DRTK_F64, DRTK_F16 = 0, 1, 2  # DRTK_F16: filter2d only
 
 
 _lib_path = None
@@ -150,6 +150,8 @@ EXPORTS = [
     "drtk_amd_grid_scatter_2d_backward",
     "drtk_amd_msi_forward",
     "drtk_amd_msi_backward",
+    "drtk_amd_filter2d_output_size",
+    "drtk_amd_filter2d",
     "drtk_amd_screen_space_uv_derivative",
     "drtk_amd_transform_pinhole",
     "drtk_amd_transform_pinhole_backward",
@@ -639,6 +641,34 @@ def msi_backward(grad_out, out, ray_o, ray_d, texture, sub_step_count=2, min_inv
             *_msi_args(ray_o, ray_d, texture, sub_step_count, min_inv_r, max_inv_r, stop_thresh), _p(gt), _stream(texture, stream)),
         "msi_backward")
     return gt
+
+
+def filter2d_output_size(size, k, up=1, down=1) -> int:
+    """Output length of one axis (host only): (size * up + pad0 + pad1 - k + down) // down -- include/drtk_amd.h."""
+    out = ctypes.c_int64(0)
+    _check(lib().drtk_amd_filter2d_output_size(_i(size), _i(k), _i(up), _i(down), ctypes.byref(out)), "filter2d_output_size")
+    return out.value
+
+
+_FILTER2D_DTYPES = {th.float32: DRTK_F32, th.float64: DRTK_F64, th.float16: DRTK_F16}
+
+
+@_on_tensor_device
+def filter2d(x, f, up=1, down=1, reflect=False, backward=False, force_generic=False, stream=None):
+    """y [N,C,OH,OW] of x [N,C,H,W] (float16, float32 or float64) filtered with the float32 taps f [k]: zero-insertion by
+    `up`, f along both axes, decimation by `down`; `backward` makes the call the gradient of the operator with the factors
+    exchanged; `force_generic` (tests) sends a tuned (up, down, k) through the generic kernel -- include/drtk_amd.h."""
+    x, f = x.contiguous(), f.contiguous()
+    assert x.ndim == 4 and f.ndim == 1 and f.dtype == th.float32, (x.shape, f.shape, f.dtype)
+    N, C, H, W = x.shape
+    k = f.shape[0]
+    y = _out(N, C, filter2d_output_size(H, k, up, down), filter2d_output_size(W, k, up, down), dtype=x.dtype, device=x.device)
+    _check(
+        lib().drtk_amd_filter2d(
+            ctypes.c_int(_FILTER2D_DTYPES[x.dtype]), _p(x), _p(f), _i(N * C), _i(H), _i(W), _i(k), _i(up), _i(down),
+            ctypes.c_int(bool(reflect)), ctypes.c_int(bool(backward)), ctypes.c_int(bool(force_generic)), _p(y), _stream(x, stream)),
+        "filter2d")
+    return y
 
 
 @_on_tensor_device

@@ -68,7 +68,9 @@ extern "C" {
 #define DRTK_AMD_VERSION_MAJOR 0
 #define DRTK_AMD_VERSION_MINOR 4
 
-typedef enum { DRTK_F32 = 0, DRTK_F64 = 1 } drtk_dtype_t;
+/* DRTK_F16 (IEEE half, storage only) is accepted by drtk_amd_filter2d alone; every other entry point answers it with
+ * DRTK_ERR_INVALID_ARGUMENT. */
+typedef enum { DRTK_F32 = 0, DRTK_F64 = 1, DRTK_F16 = 2 } drtk_dtype_t;
 
 typedef enum {
   DRTK_OK = 0,
@@ -368,6 +370,38 @@ int drtk_amd_msi_backward(
     drtk_dtype_t dtype, const void* grad_out, const void* out, const float* ray_o, const float* ray_d, const void* texture,
     int64_t N, int64_t L, int64_t H, int64_t W, int sub_step_count, double min_inv_r, double max_inv_r, double stop_thresh,
     void* grad_texture, drtk_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * filter2d -- fused separable up/down-sampling FIR filters: zero-insertion by `up`, a k-tap 1-D filter f (float32,
+ * whatever the image's type) along both axes, decimation by `down`, one kernel, no workspace; replaces filter2d_cuda
+ * (src/filter2d/filter2d.cpp, filter2d_kernel.cu) without its limits: any (up, down, k) the rule below admits (the
+ * reference's table of tuned combinations is compiled with the taps unrolled, everything else takes a generic
+ * instantiation, up to the k whose tile of one output row still fits the 160 KiB of LDS: DRTK_ERR_UNSUPPORTED beyond), a
+ * double kernel, any number of planes.
+ *   x [planes,H,W] -> y [planes,OH,OW], contiguous, written fully; planes = N * C.  Per axis (floor divisions):
+ *     pad0 = k / 2 if up == down == 1, (k - down + 1) / 2 if down != 1, else (k + up - 1) / 2
+ *     pad1 = (k - 1) / 2           |   (k - down) / 2                |      (k - up) / 2
+ *     total = pad0 + pad1,  out = (in * up + total - k + down) / down     (drtk_amd_filter2d_output_size: host only)
+ *     backward == 0:  lead = pad0,  F[j] = f[k - 1 - j]
+ *     backward != 0:  lead = k - 1 - pad0 of (up = down, down = up),  F[j] = f[j]: the call is the gradient of the
+ *                     operator with the factors exchanged, applied to its grad_out
+ *     y[o] = sum_j Z[o * down + j - lead] F[j],  Z[u] = X[u / up] where up divides u, else 0;  X outside the image is 0
+ *     (reflect == 0) or read at one reflection that does not repeat the edge (reflect != 0).
+ *   The horizontal pass runs first and is not rounded to the storage type before the vertical one; sums are float for
+ *   DRTK_F16 and DRTK_F32, double for DRTK_F64, taps in ascending order.  Bitwise reproducible.
+ * DRTK_ERR_INVALID_ARGUMENT, judged before any pointer is looked at: an unknown dtype, planes < 0, H, W, k, up or down
+ * below 1, a filter too short for the sampling factors (lead < 0 or total - lead < 0), an output smaller than 1 x 1,
+ * reflection with ceil(lead / up) or ceil((total - lead) / up) not below H and W (torch's rule for reflect padding), sizes
+ * past 2^31; then planes == 0 is DRTK_OK without a launch, and a null x, f or y is invalid.
+ * UNDER REFLECTION the `backward` call is the reference's expression, NOT the derivative of the forward: within a filter's
+ * reach of the border it reflects the incoming gradient instead of folding the border contributions back.  With zeros
+ * padding it is the exact adjoint.
+ * force_generic != 0 (TESTS ONLY) sends a tuned combination through the generic instantiation.
+ */
+int drtk_amd_filter2d_output_size(int64_t in, int64_t k, int64_t up, int64_t down, int64_t* out);
+int drtk_amd_filter2d(
+    drtk_dtype_t dtype, const void* x, const float* f, int64_t planes, int64_t H, int64_t W, int64_t k, int64_t up, int64_t down,
+    int reflect, int backward, int force_generic, void* y, drtk_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * screen_space_uv_derivative -- vt_dxdy_img [N,H,W,2,2] = [[du/dx, dv/dx],[du/dy, dv/dy]] per pixel, the
