@@ -5,6 +5,8 @@ Code written against facebookresearch/DRTK -- `from drtk import rasterize, rende
 edge_grad_estimator` (test/two_triangles.py:11), `drtk.transform(...)`, `drtk.mipmap_grid_sample(...)`,
 `from drtk.screen_space_uv_derivative import screen_space_uv_derivative`, `drtk.utils.load_torch_ops(
 "drtk.rasterize_ext")`, `import drtk.rasterize_ext` -- runs unchanged with this directory on the path.
+`drtk.transform` / `drtk.utils.project_points` take the reference's distortion modes (radial-tangential, fisheye,
+fisheye62 with its lookup table, per-view lists) on HIP tensors, and drtk.utils has its `estimate_*_fov` helpers.
 The mesh-geometry helpers of drtk.utils (`from drtk.utils import vert_normals, face_info, face_dpdt,
 vert_binormals, index`) are served by drtk_amd.geometry.  Names of the reference that are outside the path
 (grid_scatter, msi, filter2d, the pure-PyTorch `*_ref` models, drtk.utils.project_points_grad) raise an

@@ -155,6 +155,8 @@ EXPORTS = [
     "drtk_amd_screen_space_uv_derivative",
     "drtk_amd_transform_pinhole",
     "drtk_amd_transform_pinhole_backward",
+    "drtk_amd_transform_distort",
+    "drtk_amd_transform_distort_backward",
     "drtk_amd_geometry_face_forward",
     "drtk_amd_geometry_face_backward",
     "drtk_amd_geometry_face_gather",
@@ -691,6 +693,55 @@ def screen_space_uv_derivative(v, vt, vi, vti, index_img, bary_img, mask, campos
             _i(T), _i(vi_c.shape[0]), _i(H), _i(W), _p(out), _stream(bary_img, stream)),
         "screen_space_uv_derivative")
     return out
+
+
+def _transform_distort_args(v, campos, camrot, focal, princpt, coeff, fov, mode, mode_per_view, cull_outside_fov, lut, lut_spacing):
+    """The arguments drtk_amd_transform_distort and its backward share; returns (tensors kept alive, ctypes list, N, V)."""
+    dt = v.dtype
+    N = campos.shape[0]
+    assert v.ndim == 3 and v.shape[0] in (1, N) and v.shape[2] == 3, v.shape
+    keep = [v.contiguous()] + [t.to(dt).contiguous() for t in (campos, camrot, focal, princpt, coeff)] + [fov.to(dt).reshape(N).contiguous()]
+    V = v.shape[1]
+    v_sN = 0 if (v.shape[0] == 1 and N != 1) else 3 * V
+    modes = None
+    if mode_per_view is not None:
+        assert mode_per_view.dtype == th.int32 and mode_per_view.shape == (N,)
+        modes = mode_per_view.contiguous()
+    Hl = Wl = 0
+    if lut is not None:
+        assert lut.shape[:2] == (N, 2) and lut_spacing is not None and lut_spacing.shape == (N, 2)
+        lut, lut_spacing = lut.to(dt).contiguous(), lut_spacing.to(dt).contiguous()
+        Hl, Wl = lut.shape[2:]
+    keep += [modes, lut, lut_spacing]
+    vc, cp, cr, fo, pp, D, fv = keep[:7]
+    args = [ctypes.c_int(_dt(v)), _p(vc), _i(v_sN), _p(cp), _p(cr), _p(fo), _p(pp), ctypes.c_int(int(mode)), _p(modes), _p(D),
+            ctypes.c_int(int(coeff.shape[1])), _p(fv), ctypes.c_int(int(bool(cull_outside_fov))), _p(lut), _p(lut_spacing), _i(Hl), _i(Wl)]
+    return keep, args, N, V
+
+
+@_on_tensor_device
+def transform_distort(v, campos, camrot, focal, princpt, coeff, fov, mode=0, mode_per_view=None, cull_outside_fov=False,
+                      lut=None, lut_spacing=None, want_v_cam=True, stream=None):
+    """(v_pix, v_cam or None), [N,V,3]: `transform` with the distortion models -- include/drtk_amd.h.  v [N,V,3] or one
+    shared [1,V,3]; `mode` 0 pinhole, 1 radial-tangential, 2 fisheye, 3 fisheye62, or `mode_per_view` int32 [N]."""
+    keep, args, N, V = _transform_distort_args(v, campos, camrot, focal, princpt, coeff, fov, mode, mode_per_view, cull_outside_fov, lut, lut_spacing)
+    v_pix = _out(N, V, 3, dtype=v.dtype, device=v.device)
+    v_cam = _out(N, V, 3, dtype=v.dtype, device=v.device) if want_v_cam else None
+    _check(lib().drtk_amd_transform_distort(*args, _i(N), _i(V), _p(v_pix), _p(v_cam), _stream(v, stream)), "transform_distort")
+    return v_pix, v_cam
+
+
+@_on_tensor_device
+def transform_distort_backward(grad_v_pix, grad_v_cam, v, campos, camrot, focal, princpt, coeff, fov, mode=0, mode_per_view=None,
+                               cull_outside_fov=False, lut=None, lut_spacing=None, stream=None):
+    """grad_v, shaped like v ([1,V,3]: summed over the views), from grad_v_pix and / or grad_v_cam ([N,V,3] or None)."""
+    keep, args, N, V = _transform_distort_args(v, campos, camrot, focal, princpt, coeff, fov, mode, mode_per_view, cull_outside_fov, lut, lut_spacing)
+    gp = None if grad_v_pix is None else grad_v_pix.to(v.dtype).contiguous()
+    gc = None if grad_v_cam is None else grad_v_cam.to(v.dtype).contiguous()
+    assert all(g is None or g.shape == (N, V, 3) for g in (gp, gc))
+    grad_v = _out(*v.shape, dtype=v.dtype, device=v.device)
+    _check(lib().drtk_amd_transform_distort_backward(*args, _p(gp), _p(gc), _i(N), _i(V), _p(grad_v), _stream(v, stream)), "transform_distort_backward")
+    return grad_v
 
 
 GEOMETRY_CHUNK = 256  # DRTK_GEOMETRY_CHUNK of include/drtk_amd.h

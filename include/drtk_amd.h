@@ -448,6 +448,33 @@ int drtk_amd_transform_pinhole_backward(
     void* grad_v, drtk_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * transform_distort  -- transform_pinhole with the distortion camera models of drtk.transform
+ * (drtk/utils/projection.py:56-310, 618-644), one kernel each way.  The pinhole arguments as above, plus:
+ *   mode_all       0 pinhole, 1 radial-tangential, 2 fisheye, 3 fisheye62 -- the model of every view ...
+ *   mode_per_view  ... unless this device int32 [N] is given (NULL: mode_all); an id outside 0..3 projects as pinhole
+ *   coeff          [N,ncoef], ncoef 4, 5 or 8: radial-tangential (k1,k2,p1,p2[,k3[,k4,k5,k6]]); fisheye reads the first
+ *                  four; fisheye62 (k0..k5,p0,p1) needs ncoef = 8 (coefficients a row does not have read as 0)
+ *   fov            [N] the largest normalised radius (+inf allowed); not read by pinhole views
+ *   cull_outside_fov  nonzero: a fisheye62 vertex with |(x/z, y/z)| > fov gets v_pix.z = -1 (the rasterizer culls it)
+ *   lut, lut_spacing  [N,2,Hl,Wl] pixel offsets and [N,2] spacing, or NULL: added to the pixel position of fisheye62
+ *                  views, bilinear with align_corners; x is normalised by Hl - 1 and y by Wl - 1 as the reference does,
+ *                  and the offset is zero where the normalised position leaves [-1, 1]
+ * v_pix [N,V,3]; v_cam [N,V,3] or NULL.  The backward takes grad_v_pix and / or grad_v_cam ([N,V,3], either may be NULL)
+ * and gives the gradient wrt v only, as transform_pinhole_backward does; every clamp of the models has zero gradient
+ * where it is active, and on the optical axis of the fisheye models (r < 1e-8) the gradient is finite.
+ */
+int drtk_amd_transform_distort(
+    drtk_dtype_t dtype, const void* v, int64_t v_sN, const void* campos, const void* camrot, const void* focal,
+    const void* princpt, int mode_all, const int32_t* mode_per_view, const void* coeff, int ncoef, const void* fov,
+    int cull_outside_fov, const void* lut, const void* lut_spacing, int64_t Hl, int64_t Wl, int64_t N, int64_t V,
+    void* v_pix, void* v_cam, drtk_stream_t stream);
+int drtk_amd_transform_distort_backward(
+    drtk_dtype_t dtype, const void* v, int64_t v_sN, const void* campos, const void* camrot, const void* focal,
+    const void* princpt, int mode_all, const int32_t* mode_per_view, const void* coeff, int ncoef, const void* fov,
+    int cull_outside_fov, const void* lut, const void* lut_spacing, int64_t Hl, int64_t Wl, const void* grad_v_pix,
+    const void* grad_v_cam, int64_t N, int64_t V, void* grad_v, drtk_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Mesh geometry -- drtk.utils.geometry (face_info, vert_normals, face_attribute_to_vert, face_dpdt, vert_binormals;
  * pure PyTorch in the reference: drtk/utils/geometry.py) in two passes without float atomics.
  *
