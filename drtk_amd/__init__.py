@@ -1,8 +1,9 @@
 """drtk_amd -- MI355X-native differentiable rasterization hot path
 (rasterize -> render -> interpolate -> edge_grad), drop-in for the `drtk.*` functions of
 facebookresearch/DRTK on PyTorch-ROCm, plus the mesh geometry of `drtk.utils` (vertex normals,
-face info, UV Jacobians, binormals), `grid_scatter`, the `msi` background and the `filter2d` resampling filters.  Kernels: hand-written HIP for gfx950 in
+face info, UV Jacobians, binormals), `grid_scatter`, the `msi` background, the `filter2d` resampling filters and layered rendering (`rasterize_layers`, `composite_layers`).  Kernels: hand-written HIP for gfx950 in
 `drtk_amd/csrc`, C ABI in `include/drtk_amd.h`."""
+from drtk_amd.composite import composite_layers  # noqa: F401
 from drtk_amd.edge_grad_estimator import edge_grad_estimator  # noqa: F401
 from drtk_amd.filter2d import (  # noqa: F401
     FilterOptions,
@@ -49,7 +50,8 @@ __version__ = "0.1.0"
 # rows; `interpolate_masked` (interpolate with the background written as 0), `capture_step` (a whole step as a
 # HIP graph) and `set_depth_order` / `get_depth_order` (the rasterizer's depth order: the reference's source, or the
 # reference as its setup.py builds it) and `rasterize_layers` / `rasterize_layers_with_depth` (the K nearest triangles per
-# pixel, for front-to-back compositing) are this package's additions.  The mesh geometry of drtk.utils (face_info,
+# pixel) with `composite_layers` (their front-to-back compositing over a background, one kernel each way) are this package's
+# additions.  The mesh geometry of drtk.utils (face_info,
 # vert_normals, face_attribute_to_vert, face_dpdt, vert_binormals) is exported here too, and so is `grid_scatter` (the
 # splatting counterpart of grid_sample), `msi` (the multi-sphere-image background) and the eight names of `filter2d` (fused
 # alias-free up/down-sampling and low-pass filtering); the `drtk` drop-in package does not lift these three yet --
@@ -62,6 +64,7 @@ __all__ = [
     "rasterize_with_depth",
     "rasterize_layers",
     "rasterize_layers_with_depth",
+    "composite_layers",
     "render",
     "interpolate",
     "interpolate_masked",

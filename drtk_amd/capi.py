@@ -150,6 +150,8 @@ EXPORTS = [
     "drtk_amd_grid_scatter_2d_backward",
     "drtk_amd_msi_forward",
     "drtk_amd_msi_backward",
+    "drtk_amd_composite_layers",
+    "drtk_amd_composite_layers_backward",
     "drtk_amd_filter2d_output_size",
     "drtk_amd_filter2d",
     "drtk_amd_screen_space_uv_derivative",
@@ -643,6 +645,92 @@ def msi_backward(grad_out, out, ray_o, ray_d, texture, sub_step_count=2, min_inv
             *_msi_args(ray_o, ray_d, texture, sub_step_count, min_inv_r, max_inv_r, stop_thresh), _p(gt), _stream(texture, stream)),
         "msi_backward")
     return gt
+
+
+def _composite_args(color, alpha, index_img, background):
+    """(color [N,K,C,H,W], alpha [N,K,H,W], index, background, the C arguments they make): the layers of composite_layers
+    as views whose H x W planes are contiguous -- `alpha=None` takes `color` as rgba with alpha as its last channel."""
+    assert color.ndim == 5, color.shape
+    if alpha is None:
+        assert color.shape[2] >= 2, color.shape
+        color, alpha = color[:, :, :-1], color[:, :, -1]
+    elif alpha.ndim == 5:
+        assert alpha.shape[2] == 1, alpha.shape
+        alpha = alpha[:, :, 0]
+    N, K, C, H, W = color.shape
+    assert alpha.shape == (N, K, H, W) and alpha.dtype == color.dtype, (alpha.shape, color.shape)
+
+    def planes(t):
+        ok = (W <= 1 or t.stride(-1) == 1) and (H <= 1 or t.stride(-2) == W)
+        return t if ok else t.contiguous()
+
+    color, alpha = planes(color), planes(alpha)
+    if index_img is not None:
+        assert index_img.shape == (N, K, H, W) and index_img.dtype == th.int32, index_img.shape
+        index_img = index_img.contiguous()
+    bg_sN = 0
+    if background is not None:
+        assert background.shape == (N, C, H, W) and background.dtype == color.dtype, background.shape
+        if N > 1 and background.stride(0) == 0:
+            background = background[0].contiguous()
+        else:
+            background, bg_sN = background.contiguous(), C * H * W
+    args = (_p(color), (ctypes.c_int64 * 3)(*color.stride()[:3]), _p(alpha), (ctypes.c_int64 * 2)(*alpha.stride()[:2]),
+            _p(index_img), _p(background), _i(bg_sN), _i(N), _i(K), _i(C), _i(H), _i(W))
+    return color, alpha, index_img, background, args
+
+
+@_on_tensor_device
+def composite_layers(color, alpha=None, index_img=None, background=None, stream=None):
+    """(img [N,C,H,W], transmittance [N,1,H,W]): the K layers color [N,K,C,H,W] / alpha [N,K,H,W] (or rgba [N,K,C+1,H,W] with
+    `alpha=None`) composited front to back, layers whose index_img is -1 skipped, over `background` -- include/drtk_amd.h."""
+    color, alpha, index_img, background, args = _composite_args(color, alpha, index_img, background)
+    N, K, C, H, W = color.shape
+    img = _out(N, C, H, W, dtype=color.dtype, device=color.device)
+    trans = _out(N, 1, H, W, dtype=color.dtype, device=color.device)
+    _check(
+        lib().drtk_amd_composite_layers(ctypes.c_int(_dt(color)), *args, _p(img), _p(trans), _stream(color, stream)),
+        "composite_layers")
+    return img, trans
+
+
+@_on_tensor_device
+def composite_layers_backward(grad_img, grad_transmittance, color, alpha=None, index_img=None, background=None,
+                              want_color=True, want_alpha=True, want_background=True, stream=None):
+    """(grad_color, grad_alpha, grad_background), None where not wanted (or where there is no background); grad_img
+    [N,C,H,W] / grad_transmittance [N,1,H,W] may be None.  With `alpha=None` (rgba) grad_color is the one [N,K,C+1,H,W]
+    gradient, made if either of the two is wanted, and grad_alpha is None."""
+    rgba = alpha is None
+    shape, alpha_shape = color.shape, (None if rgba else alpha.shape)
+    color, alpha, index_img, background, args = _composite_args(color, alpha, index_img, background)
+    N, K, C, H, W = color.shape
+    if grad_img is not None:
+        grad_img = grad_img.contiguous()
+        assert grad_img.shape == (N, C, H, W) and grad_img.dtype == color.dtype
+    if grad_transmittance is not None:
+        grad_transmittance = grad_transmittance.contiguous()
+        assert grad_transmittance.shape == (N, 1, H, W) and grad_transmittance.dtype == color.dtype
+    gc = ga = gb = gc_view = ga_view = None
+    if rgba:
+        if want_color or want_alpha:
+            gc = _out(*shape, dtype=color.dtype, device=color.device)
+            gc_view, ga_view = gc[:, :, :-1], gc[:, :, -1]
+    else:
+        if want_color:
+            gc = gc_view = _out(*shape, dtype=color.dtype, device=color.device)
+        if want_alpha:
+            ga = _out(*alpha_shape, dtype=color.dtype, device=color.device)
+            ga_view = ga[:, :, 0] if ga.ndim == 5 else ga
+    if want_background and background is not None:
+        gb = _out(N, C, H, W, dtype=color.dtype, device=color.device)
+    gcs = (ctypes.c_int64 * 3)(*(gc_view.stride()[:3] if gc_view is not None else (0, 0, 0)))
+    gas = (ctypes.c_int64 * 2)(*(ga_view.stride()[:2] if ga_view is not None else (0, 0)))
+    _check(
+        lib().drtk_amd_composite_layers_backward(
+            ctypes.c_int(_dt(color)), _p(grad_img), _p(grad_transmittance), *args, _p(gc_view), gcs, _p(ga_view), gas, _p(gb),
+            _stream(color, stream)),
+        "composite_layers_backward")
+    return gc, ga, gb
 
 
 def filter2d_output_size(size, k, up=1, down=1) -> int:

@@ -372,6 +372,41 @@ int drtk_amd_msi_backward(
     void* grad_texture, drtk_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * composite_layers -- front-to-back compositing of K layers (what rasterize_layers + render + interpolate produce) into
+ * one image, forward and backward, one streaming kernel each way; no reference counterpart.  Per pixel, in the tensors'
+ * own type and in this order of operations (the forward is this loop bit for bit):
+ *   img = 0, T = 1;  for k = 0 .. K-1 (0 is nearest): img[c] = img[c] + (T * a_k) * color[k][c], T = T * (1 - a_k);
+ *   with a background: img[c] = img[c] + T * background[c].
+ *   color [N,K,C,H,W] and alpha [N,K,H,W]: every H x W plane contiguous, element strides between planes given as
+ *     color_strides = {view, layer, channel}, alpha_strides = {view, layer} (all >= 0) -- split tensors, one rgba tensor
+ *     [N,K,C+1,H,W] (alpha = color + C * H * W, same view / layer strides) and channel slices are read in place.
+ *   index_img [N,K,H,W] int32, contiguous, or NULL: a layer whose index is -1 is SKIPPED (it may sit between two present
+ *     layers); neither its colour nor its alpha is read, so a NaN there does not propagate.  NULL: all layers present.
+ *   background [N,C,H,W] with view stride background_sN (0: one image for all views) and contiguous views, or NULL.
+ *   img [N,C,H,W], transmittance [N,1,H,W]: contiguous, written fully.
+ *   Once T is exactly 0 the colours behind are not read (for finite inputs the result is the same bit for bit).
+ *   1 <= K <= DRTK_AMD_MAX_RASTER_LAYERS, C >= 1 (any), H * W < 2^31, any N; DRTK_F32 and DRTK_F64; tensors need the
+ *   alignment of their element only.  Judged first, before any pointer: dtype, sizes, K.  N * H * W == 0: DRTK_OK, nothing
+ *   is looked at.  No workspace, no atomics: bitwise reproducible.  Enqueues only (no sync, no host read).
+ * Backward (division-free, exact at alpha == 1): with T_k the transmittance in front of layer k, g = grad_img,
+ *   d_k = sum_c color[k][c] g[c] and R_K = grad_transmittance + sum_c background[c] g[c], for k = K-1 .. 0
+ *   grad_alpha[k] = T_k (d_k - R_{k+1}), R_k = a_k d_k + (1 - a_k) R_{k+1};  grad_color[k][c] = (T_k a_k) g[c];
+ *   grad_background[c] = T_K g[c].  grad_img [N,C,H,W] and grad_transmittance [N,1,H,W] are contiguous; either may be NULL
+ *   (taken as zeros, never read).  grad_color / grad_alpha are laid out by their own stride triples / pairs, grad_background
+ *   is [N,C,H,W] contiguous (also when the background was shared between views); each may be NULL (not wanted, its strides
+ *   are then not looked at) and each one given is written fully, zeros at skipped layers.  grad_background needs background.
+ */
+int drtk_amd_composite_layers(
+    drtk_dtype_t dtype, const void* color, const int64_t* color_strides, const void* alpha, const int64_t* alpha_strides,
+    const int32_t* index_img, const void* background, int64_t background_sN, int64_t N, int64_t K, int64_t C, int64_t H, int64_t W,
+    void* img, void* transmittance, drtk_stream_t stream);
+int drtk_amd_composite_layers_backward(
+    drtk_dtype_t dtype, const void* grad_img, const void* grad_transmittance, const void* color, const int64_t* color_strides,
+    const void* alpha, const int64_t* alpha_strides, const int32_t* index_img, const void* background, int64_t background_sN,
+    int64_t N, int64_t K, int64_t C, int64_t H, int64_t W, void* grad_color, const int64_t* grad_color_strides, void* grad_alpha,
+    const int64_t* grad_alpha_strides, void* grad_background, drtk_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * filter2d -- fused separable up/down-sampling FIR filters: zero-insertion by `up`, a k-tap 1-D filter f (float32,
  * whatever the image's type) along both axes, decimation by `down`, one kernel, no workspace; replaces filter2d_cuda
  * (src/filter2d/filter2d.cpp, filter2d_kernel.cu) without its limits: any (up, down, k) the rule below admits (the
