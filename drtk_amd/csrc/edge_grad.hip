@@ -18,7 +18,10 @@
 // Pairs are classified twice (once by each member), which costs ALU only.
 // The fused route (no v_pix_img hook: the gradient goes straight to the vertices) replaces B by a scatter of PAIRS --
 // edge_scatter_pairs_kernel -- and, in float on calls of a megapixel and more, runs that scatter inside A: ONE pass,
-// no workspace traffic (edge_dots_kernel, SCATTER; the dispatch is edge_grad_backward_fused_impl).
+// no workspace traffic (edge_dots_kernel, SCATTER; the dispatch is edge_grad_backward_fused_impl).  That pass classifies
+// its differing pairs FIRST and streams img / grad_output only where a pair's term is used: the reference selects 0 for
+// a pair of two foreground pixels of which neither lies inside the other's triangle (edge_grad_kernel.cu:338-341,
+// 391-410), and on a rendered surface nearly every differing pair is such a seam (needed_pair_flags).
 #include <cstdlib>
 
 #include "common.hpp"
@@ -89,6 +92,12 @@ __device__ __forceinline__ Row<T, VEC> load_row(
 #define DRTK_ONEPASS_WAVES 6 // waves per SIMD the one-pass kernel is compiled for (80 registers; without the bound: 85, five waves)
 #endif
 constexpr int kOnepassCap = DRTK_ONEPASS_CAP; // entries of the one-pass kernel's pair list (edge_dots_kernel, SCATTER)
+// The one-pass kernel classifies its differing pairs BEFORE it loads an image and streams only where a pair's term is
+// used (needed_pair_flags).  0 compiles the classification out (`python drtk_amd/build.py --variant out.so DRTK_EDGE_PRUNE=0`:
+// the A/B library for profiles/kernel_bench.py --lib): every differing pair is loaded for, as before.
+#ifndef DRTK_EDGE_PRUNE
+#define DRTK_EDGE_PRUNE 1
+#endif
 
 // What the SCATTER mode of edge_dots_kernel needs beside the images (the arguments of edge_scatter_pairs_kernel).
 template <typename T>
@@ -114,6 +123,11 @@ __device__ __forceinline__ void scatter_pair_round(
     const int32_t* __restrict__ vi_n, const T* __restrict__ bary_n, int64_t HW, int W, T M, int32_t* keys,
     TableAcc* vals, T* __restrict__ grad_n);
 
+template <typename T, int R>
+__device__ __forceinline__ uint32_t needed_pair_flags(
+    uint32_t flags, int lane, int strip_x0, int y0, const int32_t* __restrict__ idx_n, const T* __restrict__ v_n,
+    const int32_t* __restrict__ vi_n, int W, uint32_t* list, uint32_t* mask);
+
 // One wave = strip of 63*VEC pixels (+ VEC halo pixels in lane 63) x R rows; the WAVES waves of a workgroup are stacked vertically
 // on the same pixel columns (WAVES*R rows per workgroup), so the extra "row below" every wave needs
 // is the first row of its sibling wave and is served by this CU's L1 -- HBM sees each row
@@ -129,14 +143,30 @@ __device__ __forceinline__ void scatter_pair_round(
 // go into a wave-private LDS list of (position, term) entries, are evaluated one per lane with the axis as a compile-time
 // constant and scattered through the wave's vertex table into grad_v_pix, which the host has cleared BEFORE the launch
 // (other workgroups' atomics would race a fill spread over this grid).  Nothing crosses a wave: no workgroup barrier, no
-// workspace, and what a lane loads follows the flags -- a lane without a differing pair (and whose first pixel its left
-// neighbour does not need) loads nothing, a wave without one returns before the channel loop.
+// workspace.
+// Most differing pairs are seams between two neighbouring triangles of one surface (both pixels foreground, neither inside
+// the other's triangle: `adjacent` in eval_pair), and for those the reference selects 0 whatever the term is
+// (edge_grad_kernel.cu:338-341,391-410) -- on the bench scene 0.18 pairs per pixel differ and 0.12 % of the pixels receive
+// anything.  So the wave classifies its differing pairs first (needed_pair_flags: positions only, one pair per lane, the
+// pixel-in-triangle tests of eval_pair and nothing else) and keeps the flags of the NEEDED pairs -- a background pixel, an
+// overlap or an intersection: silhouettes and self-occlusion contours.  What a lane loads follows those flags: a lane
+// without a needed pair (and whose first pixel its left neighbour does not need) loads nothing, a wave without one returns
+// before the channel loop (four strips in five on the bench scene), and the pair phase sees the needed pairs only.
 template <typename T, int VEC, int R, int WAVES, bool SCATTER = false>
 __global__ __launch_bounds__(WAVES * kWave, SCATTER ? DRTK_ONEPASS_WAVES : 1) void edge_dots_kernel(
     const T* __restrict__ img, const T* __restrict__ grad_output, const int32_t* __restrict__ index_img, int C,
     int H, int W, int strips_x, T* __restrict__ gdx, T* __restrict__ gdy, int strip, T* __restrict__ zero_out,
     int64_t zero_count, PairArgs<T> pairs) {
   static_assert(!SCATTER || (VEC == 4 && 8 * R <= 32 && sizeof(T) == 4), "the pair phase works on four-pixel lanes of float; its flags are one register");
+  // SCATTER: wave-private LDS (the other mode has none: sizes of one element, never referenced).
+  // The list holds the flagged pairs only: a dense staging of the terms (4 KB per wave) plus a worst-case list would
+  // not fit 24 waves into a CU's 160 KB.  kOnepassCap entries of 8 bytes + the table = 6.3 KB per wave; a strip with
+  // more needed pairs than that -- an index image may differ at every pixel -- takes the list-free path below.
+  constexpr int kSlots = DRTK_EDGE_SLOTS;
+  constexpr int kCap = kOnepassCap;
+  __shared__ uint2 s_list[SCATTER ? WAVES : 1][SCATTER ? kCap : 1]; // .x = (row << 8) | pixel of the strip, .y = the pair's term
+  __shared__ int32_t t_keys[SCATTER ? WAVES : 1][SCATTER ? kSlots : 1];
+  __shared__ TableAcc t_vals[SCATTER ? WAVES : 1][SCATTER ? kSlots * 4 : 1];
   // the accumulator of the pass that follows this one (grad_v_pix of the fused route) is cleared here, spread over the
   // whole grid: one launch less per backward pass, which is what a small scene's step is made of
   if (zero_out) {
@@ -212,6 +242,18 @@ __global__ __launch_bounds__(WAVES * kWave, SCATTER ? DRTK_ONEPASS_WAVES : 1) vo
   bool load_any = any_fg;
   if constexpr (SCATTER) {
     if (__ballot(flags != 0) == 0) return; // (wave-uniform) no pair of this strip differs: nothing to add anywhere
+#if DRTK_EDGE_PRUNE
+    {
+      // the differing pairs whose term is used; the list's storage holds their positions (all of a strip's 63 x 4 x R x 2
+      // pairs fit, so this phase has no dense form), the table's keys -- initialised after it -- the lanes' verdicts
+      static_assert(2 * kCap >= (kWave - 1) * 8 * R && kSlots >= kWave, "the list's storage must hold a strip's pair positions, the keys' one word per lane");
+      const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave); // (uniform: the wave's LDS addresses stay in scalar registers)
+      flags = needed_pair_flags<T, R>(
+          flags, lane, sx * (kWave - 1) * VEC, y0, index_img + int64_t(n) * HW, pairs.v_pix + int64_t(n) * pairs.V * 3,
+          pairs.vi + int64_t(n) * pairs.vi_sN, W, reinterpret_cast<uint32_t*>(s_list[wave]), reinterpret_cast<uint32_t*>(t_keys[wave]));
+      if (__ballot(flags != 0) == 0) return; // (wave-uniform) seams only: the host has cleared grad_v_pix, nothing to add
+    }
+#endif
     // pixel 3 of a lane pairs with the NEXT lane's first pixel, so that lane loads for it
     uint32_t h3 = 0;
 #pragma unroll
@@ -253,15 +295,7 @@ __global__ __launch_bounds__(WAVES * kWave, SCATTER ? DRTK_ONEPASS_WAVES : 1) vo
   }
   if constexpr (SCATTER) {
     // ---- the pair phase of edge_scatter_pairs_kernel on this wave's own pairs; every lane stays to the end (ballots, DPP scans)
-    constexpr int kSlots = DRTK_EDGE_SLOTS;
-    // The list holds the flagged pairs only: a dense staging of the terms (4 KB per wave) plus a worst-case list would
-    // not fit 24 waves into a CU's 160 KB.  kOnepassCap entries of 8 bytes + the table = 6.3 KB per wave; a strip with
-    // more differing pairs than that -- an index image may differ at every pixel -- takes the list-free path below.
-    constexpr int kCap = kOnepassCap;
-    __shared__ uint2 s_list[WAVES][kCap]; // .x = (row << 8) | pixel of the strip, .y = the pair's term
-    __shared__ int32_t t_keys[WAVES][kSlots];
-    __shared__ TableAcc t_vals[WAVES][kSlots * 4];
-    const int wave = threadIdx.x / kWave;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave); // (uniform: the wave's LDS addresses stay in scalar registers)
     const int32_t* idx_n = index_img + int64_t(n) * HW;
     const T* v_n = pairs.v_pix + int64_t(n) * pairs.V * 3;
     const int32_t* vi_n = pairs.vi + int64_t(n) * pairs.vi_sN;
@@ -322,7 +356,7 @@ __global__ __launch_bounds__(WAVES * kWave, SCATTER ? DRTK_ONEPASS_WAVES : 1) vo
         }
       }
     } else {
-      // More than kCap of the strip's at most 63 x 4 x R x 2 pairs differ: compaction has little to gain, so each lane
+      // More than kCap of the strip's at most 63 x 4 x R x 2 pairs are needed: compaction has little to gain, so each lane
       // keeps its own pairs -- for each of its 4 R pixels and each axis one round in which every lane with that flag set
       // takes its pair (at least half of the lanes on average).  Any density; the list's storage holds the terms
       // meanwhile, all of them (dense: entry k of lane l at [k][l]), so that they do not occupy registers in the rounds.
@@ -783,6 +817,61 @@ __device__ __forceinline__ void scatter_pair_round(
   }
 }
 
+// Classification phase of edge_dots_kernel's SCATTER mode: of the wave's differing pairs (`flags`, the kernel's layout),
+// those whose term reaches the output.  eval_pair discards the term of an `adjacent` pair -- both pixels foreground,
+// neither inside the other's triangle -- with a select, and scatter_pair_round then drops the pair (a_on / b_on); every
+// other pair is needed.  The verdict is eval_pair's own: the same load_tri, the same pix_in_tri on the same arguments
+// (no contraction, no fast-math: the same bits), and nothing else of it -- no normals, square roots, barycentrics.
+// The pairs' positions are compacted into `list` (uint32 per pair: owner lane << 5 | flag bit; row-major per axis, so
+// that a round's index gathers run along image rows) and taken one per lane; a pair with a background pixel is needed
+// without a look at its triangle.  A needed pair sets its bit in its owner's word of `mask` (one word per lane).
+// Wave-collective; `list` and `mask` are wave-private LDS, free for other use on return.
+template <typename T, int R>
+__device__ __forceinline__ uint32_t needed_pair_flags(
+    uint32_t flags, int lane, int strip_x0, int y0, const int32_t* __restrict__ idx_n, const T* __restrict__ v_n,
+    const int32_t* __restrict__ vi_n, int W, uint32_t* list, uint32_t* mask) {
+  const unsigned long long lt = (1ull << lane) - 1ull;
+  mask[lane] = 0;
+  int n_all = 0;
+#pragma unroll
+  for (int g = 0; g < 2 * R; ++g) {
+    const uint32_t f = (flags >> (4 * g)) & 15u;
+    int t;
+    int pos = n_all + prefix4(__popc(f), lt, t);
+    n_all += t;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (f & (1u << j)) list[pos++] = static_cast<uint32_t>((lane << 5) | (4 * g + j));
+    }
+  }
+  wave_lds_sync();
+  for (int t0 = 0; t0 < n_all; t0 += kWave) {
+    const int t = t0 + lane;
+    if (t < n_all) {
+      const uint32_t entry = list[t];
+      const int bit = static_cast<int>(entry & 31u), owner = static_cast<int>(entry >> 5);
+      const bool vertical = bit >= 4 * R;
+      const int k = vertical ? bit - 4 * R : bit;
+      const int xa = strip_x0 + owner * 4 + (k & 3), ya = y0 + (k >> 2);
+      const int xb = vertical ? xa : xa + 1, yb = vertical ? ya + 1 : ya;
+      const int64_t pa = int64_t(ya) * W + xa;
+      const int32_t ia = idx_n[pa], ib = idx_n[vertical ? pa + W : pa + 1];
+      bool need = true;
+      if (ia >= 0 && ib >= 0) { // `both` of eval_pair
+        TriInfo<T> ta, tb;
+        load_tri<T>(v_n, vi_n, ia, ta);
+        load_tri<T>(v_n, vi_n, ib, tb);
+        const bool a_in_b = pix_in_tri(tb, xa, ya);
+        const bool b_in_a = pix_in_tri(ta, xb, yb);
+        need = a_in_b || b_in_a; // not `adjacent`
+      }
+      if (need) atomicOr(&mask[owner], 1u << bit);
+    }
+  }
+  wave_lds_sync();
+  return mask[lane];
+}
+
 // Fused pass B for the default route of drtk.edge_grad_estimator (no v_pix_img hook): instead of
 // materialising grad_v_pix_img [N,3,H,W] (80 % exact zeros) for a separate C=3 interpolate backward to
 // scatter, the contributions are multiplied by the pixel's barycentrics and scattered to the triangle's
@@ -1022,6 +1111,13 @@ inline bool aligned_to(const void* p, size_t a) {
 //   8 x 2048^2, C 16, 250k             0.664-0.666 | 0.715-0.762
 //   2 x 4096^2, C  3, 1M               0.293-0.295 | 0.371-0.381   (small C: the pair phase dominates, and it no longer
 //                                                                   re-reads the index rows or fetches the terms)
+// and with the classification phase (DRTK_EDGE_PRUNE; profiles/r08/edge_prune_ab.txt; one pass, pruned | one pass of the
+// parent commit, another box):
+//   8 x 2048^2, C 16, 100k triangles   0.251-0.256 | 0.625-0.629
+//   8 x 2048^2, C 16, 250k             0.275-0.277 | 0.653-0.662
+//   2 x 4096^2, C  3, 1M               0.136-0.138 | 0.295-0.299
+//   2 x 1024^2, C 16, random ids       1.783-1.788 | 1.697-1.699   (every pair differs and hardly any is a seam: the
+//                                                                   classification is pure overhead, 5 %)
 //   4 x 512^2,  C  3, 10k              0.027-0.031 | 0.031-0.033
 //   2 x 512^2,  C  3, 10k              0.021-0.024 | 0.026-0.028
 //   2 x 128^2,  C 16, 10k              0.033-0.040 | 0.036
