@@ -612,7 +612,7 @@ __global__ __launch_bounds__(kBlock, sizeof(T) == 8 ? DRTK_MIP_FWD_OCC_F64 : (CB
             (static_cast<unsigned>(iy_nw) < static_cast<unsigned>(lh[s] - 1));
         // corner weights (bilinear_quad: (ix_se - ix) with ix_se = ix_nw + 1, an exact float) times the level's weight
         const T wx1 = (fx_floor + T(1)) - ix, wx0 = ix - fx_floor;
-        const int plane = lw[s] * lh[s]; // <= kLeanMaxPlane (the dispatch): cc * plane + offset fits 32 bits
+        const int plane = lw[s] * lh[s]; // <= kMaxPlane32 (the dispatch): cc * plane + offset fits 32 bits
         const GlobalPtr<const T> b = lbase[s] + int64_t(c0) * plane;
         // Round 6: the tap's loads and fmas run under `interior` -- ONE exec-mask region per (tap, level).  Round 5 let the
         // other lanes (no tap i, a border tap, a NaN coordinate, a dead level) run the same loads at offset 0 with weight 0:
@@ -647,7 +647,7 @@ __global__ __launch_bounds__(kBlock, sizeof(T) == 8 ? DRTK_MIP_FWD_OCC_F64 : (CB
             const T aq = s == 0 ? alpha_2 : alpha_1;
 #pragma unroll
             for (int cc = 0; cc < CB; ++cc) {
-              const GlobalPtr<const T> pch = b + cc * plane; // (cc <= 3, plane <= kLeanMaxPlane)
+              const GlobalPtr<const T> pch = b + cc * plane; // (cc <= 3, plane <= kMaxPlane32)
               if (q.o_nw >= 0) acc[cc] += pch[q.o_nw] * q.nw * aq;
               if (q.o_ne >= 0) acc[cc] += pch[q.o_ne] * q.ne * aq;
               if (q.o_sw >= 0) acc[cc] += pch[q.o_sw] * q.sw * aq;
@@ -781,18 +781,31 @@ __global__ __launch_bounds__(kBlock) void mipmap_backward_kernel(
   store_grid_grad<T>(grad_grid, ggl, n, index - n * HW, acc_x, acc_y);
 }
 
-// Backward, bilinear, C <= 4: LDS-windowed accumulation of the texture gradient.
-// The direct kernel above is bound by the float-atomic REQUEST rate (~20 G/s): every (tap, level, corner,
-// channel) is one atomic instruction touching ~5 64-byte segments.  Here a workgroup owns a 16 x 16 PIXEL
-// tile, whose taps land in a compact texel window on the two or three mip levels its pixels select; the
-// window (32 x 32 texels per level, 3 levels from the tile's finest level) is accumulated in LDS with
-// ds_add_f32 and flushed once, row-major, so the global atomics are coalesced and each touched texel costs
-// one request per tile instead of one per tap.  Corners outside the window, or on other levels, go to
-// global memory directly, so any uv field is handled.
-// Pixel tile: kTileW x kTileH pixels, one thread each.  16 x 16 is a sweet spot, same-box A/B on the textured benchmark /
-// kernel_bench at 1 and 4 texels per pixel: 16 x 32 (8 waves per workgroup over the same 48 KB of windows, twice the
-// waves per CU) 3.11 / 4.61 / 10.8 ms against 1.94 / 2.99 / 8.13 -- the taller tile's taps spread over more texels than a
-// window holds, and its misses cost rounds; 16 x 8: 2.9 ms -- the per-tile costs (window init + flush scan, five
+// ---- Backward, bilinear, any padding, any C, float and double: the LEAN tile kernel (round 5; reflection and double: round 6)
+// The direct kernel above is bound by the float-atomic REQUEST rate (~20 G/s): every (tap, level, corner, channel) is one
+// atomic instruction touching ~5 64-byte segments.  Here a workgroup owns a 16 x 16 PIXEL tile, whose taps land in a compact
+// texel window on the two mip levels its pixels select; the windows (kWinLevels shaped slots, double accumulators) are
+// accumulated in LDS and flushed once, row-major, so the global atomics are coalesced and each touched texel costs one
+// request per tile instead of one per tap.  Taps the windows did not hold stay pending and get the windows in a further round
+// (up to DRTK_MIP_LEAN_ROUNDS); what is pending after the last one goes to global memory corner by corner, so any uv field
+// is handled.
+//   * the level tables, the placement cells and the windows' zero-fill are issued UNDER the loads of the upstream gradient /
+//     uv / Jacobian, in front of the first barrier;
+//   * reference level and window origins come out of ONE phase: every wave reduces the extremes of its taps per ABSOLUTE
+//     level into s_lox / s_loy / s_hiy[d]; after one barrier the origins are read into scalar registers;
+//   * taps of a pixel that land in the same 2 x 2 cell are merged in registers before they touch LDS;
+//   * the flush reads only the window rows a round can have written;
+//   * the tap loop is written the way the lean forward is (one straight line per (tap, level) for the whole wave: no Quad, no
+//     per-corner logic, regrouped products, texture channels a template parameter) -- for the instructions, and for the
+//     REGISTERS: the tile kernel of round 4 sat at 151-168 VGPRs = 3 waves per SIMD with every tile's chain (loads -> barrier
+//     -> placement -> barrier -> taps -> barrier -> flush) exposed; at <= 128 a CU holds four tiles instead of three.
+// Sums regrouped, never dropped: same results to rounding (fixtures, known answers, fuzz_mipmap, fuzz_mipmap_snapped).
+// PAD / ALIGN: padding mode and align_corners as compile-time constants (the coordinate pipeline of every tap branches on
+// them: SQ counters of the runtime-parameter version showed 490 scalar and 950 vector instructions per wave).
+// Pixel tile: kTileW x kTileH pixels, one thread each.  16 x 16 is a sweet spot, same-box A/B of round 4's tile kernel on the
+// textured benchmark / kernel_bench at 1 and 4 texels per pixel: 16 x 32 (8 waves per workgroup over the same 48 KB of
+// windows, twice the waves per CU) 3.11 / 4.61 / 10.8 ms against 1.94 / 2.99 / 8.13 -- the taller tile's taps spread over more
+// texels than a window holds, and its misses cost rounds; 16 x 8: 2.9 ms -- the per-tile costs (window init + flush scan, five
 // barriers) are paid twice as often.
 constexpr int kTileW = 16;
 #ifndef DRTK_MIP_TILE_H
@@ -800,636 +813,9 @@ constexpr int kTileW = 16;
 #endif
 constexpr int kTileH = DRTK_MIP_TILE_H;
 constexpr int kMipBlock = kTileW * kTileH;
-#ifndef DRTK_MIP_WIN
-#define DRTK_MIP_WIN 32
-#endif
-#ifndef DRTK_MIP_WINB
-#define DRTK_MIP_WINB DRTK_MIP_WIN
-#endif
-constexpr int kWin = DRTK_MIP_WIN;   // texel window side on the tile's finest level
-constexpr int kWinB = DRTK_MIP_WINB; // ... and on the next one (even: the flush reads cells in pairs)
-constexpr int kWinLevels = 2;
-#ifndef DRTK_MIP_WINPAD
-#define DRTK_MIP_WINPAD 0
-#endif
-// Extra cells per window row and per channel plane (even: the flush reads cells in 16-byte pairs).  A 32-cell row is 256
-// bytes, one sweep of the 64 LDS banks, so the south corners of a tap share the banks of its north corners and so do the
-// pixel rows of a wave -- SQ_LDS_BANK_CONFLICT + SQ_LDS_ADDR_CONFLICT are more than half of this kernel's LDS-active
-// cycles -- but the LDS pipe is only ~11 % busy and padding the strides to 34 cells bought nothing: 2.23 vs 2.17 ms on the
-// textured benchmark, 4.65 vs 4.58 and 11.9 vs 11.8 ms on the minified scenes of profiles/kernel_bench.py.  Neither did
-// walking the 4C cells of a tap in a per-lane rotated order, which removes the same-address meetings of neighbouring
-// pixels on a magnified texture (2.16 vs 2.23 ms).  Kept as a switch for the next look at this kernel.
-constexpr int kWinPad = DRTK_MIP_WINPAD;
-__host__ __device__ constexpr int win_side(int l) { return l == 0 ? kWin : kWinB; }
-__host__ __device__ constexpr int win_stride(int l) { return win_side(l) + kWinPad; }
-__host__ __device__ constexpr int win_cells(int l) { return win_side(l) * win_stride(l) + kWinPad; } // per channel (the channels of a cell in different banks, too)
-__host__ __device__ constexpr int win_cells_before(int l) { return l == 0 ? 0 : win_cells(0) + (l - 1) * win_cells(1); } // per channel
-constexpr int kWinCells = win_cells_before(kWinLevels);
-// `dbg` (diagnostics, profiles/kernel_bench.py --flags): 1 = no texture-gradient accumulation, 2 = no texel reads,
-// 4 = no flush.  Where the 6.0 ms of the bench shape go (finer timing-only variants, r01): the global-atomic fallback for
-// corners outside the windows ~1.5 ms, the four LDS adds ~0.8 ms, the flush 0.5 ms, texel reads 0.2 ms, everything else
-// (tap set-up, window bookkeeping, barriers) the rest.  Flag 1 alone overstates the atomics: it also drops the fallback
-// and lets the compiler delete the bookkeeping (2.2 ms remain).  On that scene 91.5 % of the (tap, level) pairs hit the
-// windows, 7.0 % miss by POSITION (anisotropic taps: a 16-pixel tile spans up to 16 * N * 2 texels along the major
-// axis), 1.5 % by level; 16 % of the tiles have a miss and the worst 1 % hold a third of them (atlas seam, silhouette).
-// Measured dead end: the same LDS split 2048 / 768 / 256 cells over the levels with every window shaped like its tile's
-// bounding box -- 1-4 % (6.06 -> 6.02 ms at 1 texel/px, 11.5 -> 11.0 at 4), one outlier pixel stretches the box.
-
-// Round 4, where the time is WITHOUT the scatter (ablation flags 16 = no grid-gradient products, 32 = no tap loop at all, on
-// top of 1 / 2 / 4 / 8; textured benchmark, 1.96 ms with the 0.14 ms zero-fill of the pyramid): no accumulation, texel reads,
-// flush or rounds 1.02; also no grid-gradient products 0.95; no tap loop at all 0.75 -- of which 0.14 the fill and 0.3 the
-// 1.5 GB of upstream gradient, uv, Jacobian and grid gradient at stream speed.  Two structural variants were measured
-// against that and NOT kept: wave-private windows without any workgroup barrier (mipmap_backward_wave_kernel below; same
-// 3 waves per SIMD, same 1.0 ms floor, 2.52 vs 1.95 ms at C = 3: the floor is per-(tap, level) arithmetic and the stream,
-// not barriers), and persistent workgroups that request the next tile's upstream gradient before working on the current
-// one (2.20 vs 1.96 ms; the floor with no tap loop rose from 0.75 to 0.98: the hardware's own workgroup dispatch balances
-// the mix of background and silhouette tiles better than a static stride, and the job loop costs registers).  Also
-// nothing: the window products in double (7 conversions + 12 double multiplications instead of 12 + 12) and the grid
-// gradient's eight products regrouped into 10 operations per channel with written-out fmas (1.967 vs 1.955 ms).
-// PAD / ALIGN: padding mode and align_corners as compile-time constants (the coordinate pipeline of every tap branches on
-// them: SQ counters of the runtime-parameter version showed 490 scalar and 950 vector instructions per wave).
-// (mipmap_backward_tiled_kernel, the kernel these notes are about -- square 32 x 32 windows, the general tap loop, five
-// barriers per tile -- was replaced in round 5 by the two kernels below: git history, profiles/NOTES.md R5.2.)
-
-// ---- round 5: the tile kernel with a shorter chain per tile (reflection padding, double; everything else: the lean kernel
-// further down) -----------------------------------------------------------------------------------------------------------
-// The ablation of round 4 had left 0.75 of the tile kernel's 1.95 ms outside the tap loop and ~0.95 in the scatter (LDS
-// accumulation, rounds, flush), with the waves parked half of their life at 3 per SIMD.  Changes against round 4's
-// mipmap_backward_tiled_kernel:
-//   * the level tables, the placement cells and the windows' zero-fill are issued UNDER the loads of the upstream
-//     gradient / uv / Jacobian, in front of the first barrier (the level-0 size that the tap set-up needs comes from the
-//     kernel argument) -- one barrier and one exposed phase less;
-//   * reference level and window origins come out of ONE phase: every wave reduces the extremes of its taps per
-//     ABSOLUTE level (one to three levels per wave) into s_lox / s_loy / s_hiy[d]; after one barrier ref = s_ref and the
-//     origins are s_lox[ref + l], read into scalar registers -- two barriers less;
-//   * taps of a pixel that land in the same 2 x 2 cell are merged in registers before they touch LDS (run_cell / run_w);
-//   * the flush reads only the window rows the first round can have written (s_hiy).
-// Sums regrouped, never dropped: same results to rounding (fixtures, known answers, fuzz_mipmap, fuzz_mipmap_snapped).
-#ifndef DRTK_MIP_T2_OCC
-#define DRTK_MIP_T2_OCC 3
-#endif
-#ifndef DRTK_MIP_HOPELESS
-#define DRTK_MIP_HOPELESS 0 // measured and left OFF (below): -1.5 % on the textured benchmark at its best threshold, +3 ... +10 % on minified scenes
-#endif
-#ifndef DRTK_MIP_HOPELESS_PAIRS
-#define DRTK_MIP_HOPELESS_PAIRS 96 // (a round costs about as much as sending this many pairs' 12 atomics each to global memory)
-#endif
-template <typename T, int PAD, bool ALIGN>
-// (3 workgroups per CU by registers as by LDS; reflection padding needs ~200: 2)
-__global__ __launch_bounds__(kMipBlock, sizeof(T) == 8 ? 1 : (PAD == 2 ? 2 : DRTK_MIP_T2_OCC)) void mipmap_backward_tiled2_kernel(
-    LevelTable lv, int mipmaps, const T* __restrict__ grad_out, const T* __restrict__ grid, GridLayout gl,
-    const T* __restrict__ vt, int H, int W, int C, int tiles_x, int max_aniso,
-    bool force_max_aniso, bool clip_grad, T* __restrict__ grad_grid, GridLayout ggl, int strip, int dbg) {
-  constexpr int padding = PAD;
-  constexpr bool align_corners = ALIGN;
-  __shared__ double s_f[kTapTab * kTapTab];
-  __shared__ const void* s_ptr[kMaxLevels];
-  __shared__ void* s_grad[kMaxLevels];
-  __shared__ int s_h[kMaxLevels], s_w[kMaxLevels];
-  __shared__ long long s_sn[kMaxLevels];
-  __shared__ int s_ref, s_npend, s_ox[kWinLevels], s_oy[kWinLevels], s_hx[kWinLevels], s_hy[kWinLevels];
-  // first-round placement per ABSOLUTE level (so that the reference level and the origins come out of ONE phase):
-  // bounding box of the north-west texels of the tile's taps on level d
-  __shared__ int s_lox[kMaxLevels + 1], s_loy[kMaxLevels + 1], s_hix[kMaxLevels + 1], s_hiy[kMaxLevels + 1];
-  extern __shared__ __attribute__((aligned(16))) unsigned char s_win_raw[];
-  double* const s_win = reinterpret_cast<double*>(s_win_raw);
-  const int tid = threadIdx.x;
-  const int n = blockIdx.y;
-  const int tile = tile_index(strip);
-  const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
-  const int px = tx * kTileW + (tid & (kTileW - 1)), py = ty * kTileH + tid / kTileW;
-  const bool valid = px < W && py < H;
-  const int64_t HW = int64_t(H) * W;
-  const int64_t index = int64_t(n) * HW + int64_t(py) * W + px;
-  // the pixel's upstream gradient, uv and Jacobian: one batch of loads ...
-  T go[4] = {T(0), T(0), T(0), T(0)};
-  if (valid) {
-    const T* gout_px = grad_out + int64_t(n) * C * HW + (int64_t(py) * W + px);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      if (c < C) go[c] = gout_px[int64_t(c) * HW];
-    }
-  }
-  PixelUV<T> uv = {};
-  const int64_t pix = int64_t(py) * W + px;
-  if (valid) uv = load_pixel_uv<T>(grid, gl, vt, n, pix, index);
-  // ... and under them everything that needs no data: the tables, the placement cells, the windows' zero-fill (a tile
-  // that turns out to have no upstream gradient has zeroed its windows for nothing; the stores wait for nobody)
-  stage_tap_table(s_f);
-  if (tid < kMaxLevels) {
-    const int i = tid < mipmaps ? tid : 0;
-    s_ptr[tid] = lv.ptr[i], s_grad[tid] = lv.grad[i], s_sn[tid] = lv.sn[i], s_h[tid] = lv.h[i], s_w[tid] = lv.w[i];
-  }
-  if (tid <= kMaxLevels) s_lox[tid] = s_loy[tid] = INT32_MAX, s_hix[tid] = s_hiy[tid] = INT32_MIN;
-  if (tid == 0) s_ref = kMaxLevels;
-  {
-    double2* w2 = reinterpret_cast<double2*>(s_win);
-    const double2 z = {0.0, 0.0};
-    for (int i = tid; i < C * kWinCells / 2; i += kMipBlock) w2[i] = z;
-  }
-  const bool has_go = go[0] != T(0) || go[1] != T(0) || go[2] != T(0) || go[3] != T(0);
-  if (!__syncthreads_or(has_go)) { // (also publishes the tables and the zero-fill)
-    if (valid) store_grid_grad<T>(grad_grid, ggl, n, pix, T(0), T(0));
-    return;
-  }
-
-  Taps<T> t = {};
-  if (has_go) t = setup_taps<T>(uv, lv.h[0], lv.w[0], mipmaps, max_aniso, force_max_aniso, clip_grad);
-  const int n_lv = mipmaps > 1 ? 2 : 1;
-  const T alpha_1 = has_go ? t.a / t.n : T(0);
-  const T alpha_2 = has_go ? static_cast<T>((1.0 - t.a) / t.n) : T(0);
-  // A (pixel, level) whose weighted upstream gradient is zero in every channel adds nothing anywhere (every term is
-  // +-0 * finite): the masked background of a silhouette tile, and the second level of a magnified pixel (a == 0).
-  // Such pairs neither place the windows nor run their taps.
-  bool live[2];
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    const T alpha = s == 0 ? alpha_2 : alpha_1;
-    live[s] = false;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) live[s] = live[s] || (go[c] * alpha != T(0));
-    live[s] = live[s] && s < n_lv;
-  }
-  auto tap_xy = [&](int i, T& x, T& y) {
-    const double f = tap_f(s_f, i, t.n);
-    x = t.u + static_cast<T>(t.du * f);
-    y = t.v + static_cast<T>(t.dv * f);
-  };
-  // window origins: the taps of a pixel are collinear, so their extreme texels are those of the first and the last
-  // tap.  ANY origin is correct -- a corner is windowed iff its exact cell lies inside, tested below -- so the origin
-  // comes from a short form of the coordinate pipeline: unnormalise, clamp to the level, floor (the exact north-west
-  // texel for zeros / border padding; under reflection padding taps beyond the border miss the window).
-  auto texel_floor = [&](T coord, int size) -> int {
-    T unused;
-    const T c = unnormalize(coord, size, align_corners, &unused);
-    const T lo = padding == 0 ? T(-1) : T(0);
-    return static_cast<int>(floor(fmin(fmax(c, lo), static_cast<T>(size - 1)))); // fmax(NaN, lo) = lo
-  };
-  {
-    // ONE phase for the reference level and the origins: the extremes go into cells of their ABSOLUTE level, wave by
-    // wave over the (one to three) levels a wave's pixels use
-    int lo_x[2] = {INT32_MAX, INT32_MAX}, lo_y[2] = {INT32_MAX, INT32_MAX}, hi_x[2] = {INT32_MIN, INT32_MIN}, hi_y[2] = {INT32_MIN, INT32_MIN};
-    if (live[0] || live[1]) {
-      for (int e = 0; e < 2; ++e) {
-        T x, y;
-        tap_xy(e == 0 ? 0 : t.n - 1, x, y);
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-          if (s < n_lv && live[s]) {
-            const int ox = texel_floor(x, s_w[t.d1 + s]), oy = texel_floor(y, s_h[t.d1 + s]);
-            lo_x[s] = min(lo_x[s], ox), lo_y[s] = min(lo_y[s], oy), hi_x[s] = max(hi_x[s], ox), hi_y[s] = max(hi_y[s], oy);
-          }
-        }
-      }
-    }
-    const int d_lo = wave_min_i32(live[0] ? t.d1 : live[1] ? t.d1 + 1 : kMaxLevels);
-    const int d_hi = wave_max_i32(live[1] ? t.d1 + 1 : live[0] ? t.d1 : -1);
-    for (int d = d_lo; d <= d_hi; ++d) { // wave-uniform
-      const bool m0 = live[0] && t.d1 == d, m1 = live[1] && t.d1 + 1 == d;
-      const int a = wave_min_i32(min(m0 ? lo_x[0] : INT32_MAX, m1 ? lo_x[1] : INT32_MAX));
-      const int b = wave_min_i32(min(m0 ? lo_y[0] : INT32_MAX, m1 ? lo_y[1] : INT32_MAX));
-      const int e = wave_max_i32(max(m0 ? hi_y[0] : INT32_MIN, m1 ? hi_y[1] : INT32_MIN));
-      const int g = wave_max_i32(max(m0 ? hi_x[0] : INT32_MIN, m1 ? hi_x[1] : INT32_MIN));
-      if ((tid & (kWave - 1)) == 0 && a != INT32_MAX) {
-        atomicMin(&s_lox[d], a);
-        atomicMin(&s_loy[d], b);
-        atomicMax(&s_hix[d], g);
-        atomicMax(&s_hiy[d], e);
-      }
-    }
-    if ((tid & (kWave - 1)) == 0 && d_lo < kMaxLevels) atomicMin(&s_ref, d_lo);
-  }
-  __syncthreads();
-  const int ref = s_ref;
-  // ---- the two window SLOTS (round 5: shaped, not square).  Slot l holds level ref + l.  The windows' memory is
-  // kWinLevels x kWinSlotCells accumulators per channel; a tile with no live tap on level ref + 1 -- every tile of a magnified
-  // texture -- gives it all to slot 0; a slot is 2^sx cells wide, sx chosen by the bounding box of the taps it has to
-  // hold (16 ... 128 wide: the elongated footprints of a limb tile fit where a 32 x 32 square needed four rounds).
-  // Wave-uniform values: scalar registers.
-  constexpr int kWinSlotCells = kWin * kWin;
-  static_assert(kWinPad == 0 && kWinB == kWin && kWinCells == kWinLevels * kWinSlotCells, "the shaped slots re-partition the square windows' memory");
-  int wox[kWinLevels], woy[kWinLevels], wsx[kWinLevels], wny[kWinLevels], wcells[kWinLevels], win_rows[kWinLevels];
-  auto shape_slots = [&](const int (&lox)[kWinLevels], const int (&loy)[kWinLevels], const int (&hix)[kWinLevels], const int (&hiy)[kWinLevels], bool all_rows) {
-    const bool two = lox[1] != INT32_MAX;
-#pragma unroll
-    for (int l = 0; l < kWinLevels; ++l) {
-      wox[l] = lox[l], woy[l] = loy[l];
-      wcells[l] = l == 0 ? (two ? kWinSlotCells : kWinLevels * kWinSlotCells) : (two ? kWinSlotCells : 0);
-      const long long need_w = static_cast<long long>(hix[l]) - lox[l] + 2, need_h = static_cast<long long>(hiy[l]) - loy[l] + 2;
-      int sx = need_w <= 16 ? 4 : need_w <= 32 ? 5 : (need_w <= 64 && need_h <= (wcells[l] >> 6)) ? 6 : (need_w > 64 && need_h <= (wcells[l] >> 7)) ? 7 : 5;
-      if (lox[l] == INT32_MAX) sx = 5;
-      wsx[l] = sx;
-      wny[l] = wcells[l] > 0 ? (wcells[l] >> sx) : 1; // (1: no cell passes the row test of an empty slot)
-      win_rows[l] = (all_rows || need_h > wny[l]) ? wny[l] : static_cast<int>(need_h < 0 ? 0 : need_h);
-      if (wcells[l] == 0) win_rows[l] = 0;
-    }
-  };
-  {
-    int lox[kWinLevels], loy[kWinLevels], hix[kWinLevels], hiy[kWinLevels];
-#pragma unroll
-    for (int l = 0; l < kWinLevels; ++l) {
-      const int d = min(ref + l, kMaxLevels);
-      lox[l] = __builtin_amdgcn_readfirstlane(s_lox[d]), loy[l] = __builtin_amdgcn_readfirstlane(s_loy[d]);
-      hix[l] = __builtin_amdgcn_readfirstlane(s_hix[d]), hiy[l] = __builtin_amdgcn_readfirstlane(s_hiy[d]);
-    }
-    // rows the first round can touch: exact for zeros / border padding, where the extremes are the true north-west texels;
-    // under reflection padding every row
-    shape_slots(lox, loy, hix, hiy, padding == 2);
-  }
-  // cell of a north-west texel in slot l (the other three corners are +1, +stride, +stride+1), or -1
-  auto slot_cell = [&](int l, int ix_nw, int iy_nw) -> int {
-    if (l < 0 || l >= kWinLevels) return -1;
-    const int wx = ix_nw - (l == 0 ? wox[0] : wox[1]), wy = iy_nw - (l == 0 ? woy[0] : woy[1]);
-    const int sx = l == 0 ? wsx[0] : wsx[1], ny = l == 0 ? wny[0] : wny[1];
-    return (static_cast<unsigned>(wx) < (1u << sx) - 1u && static_cast<unsigned>(wy) < static_cast<unsigned>(ny - 1)) ? (wy << sx) + wx : -1;
-  };
-  auto slot_stride = [&](int l) -> int { return 1 << (l == 0 ? wsx[0] : wsx[1]); };
-  auto slot_chan = [&](int l) -> int { return l == 0 ? wcells[0] : wcells[1]; };  // cells per channel
-  auto slot_base = [&](int l) -> int { return l == 0 ? 0 : C * wcells[0]; };        // first cell of the slot's channel 0
-
-  // (tap, level) pairs that find no window cell in this round: not sent to global memory one corner and channel at a
-  // time -- scattered float atomics of single lanes, 0.72 of this kernel's 2.2 ms on the textured benchmark although
-  // only a few per cent of the taps miss -- but remembered (per level of the pixel: did any tap miss, and where) for a
-  // further round with the windows moved onto them (below, up to DRTK_MIP_ROUNDS rounds).
-  // (where they missed is NOT carried through the tap loop -- six registers at its bound: a round recomputes the
-  // north-west texels of its pending taps, which it walks anyway)
-  uint32_t pending = 0; // bit 2 i + s: tap i on the pixel's level s found no window cell yet (taps >= 16 are never deferred)
-  if (valid) {
-    T acc_x = T(0), acc_y = T(0);
-    // the pixel's two levels: sizes and base pointers once, not per tap
-    // (the gradient planes' base, which only the rare fallbacks to global memory need, is rebuilt from the LDS table there)
-    int lv_h[2], lv_w[2];
-    GlobalPtr<const T> lv_inp[2];
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const int d = live[s] ? t.d1 + s : 0;
-      lv_h[s] = s_h[d], lv_w[s] = s_w[d];
-      lv_inp[s] = (GlobalPtr<const T>)(static_cast<const T*>(s_ptr[d]) + int64_t(n) * s_sn[d]);
-    }
-    auto grad_base = [&](int d, int64_t plane) -> GlobalPtr<T> { return (GlobalPtr<T>)(static_cast<T*>(s_grad[d]) + int64_t(n) * C * plane); };
-    // (one run slot, for the pixel's FINER level: a magnified pixel has no other live level, and the taps of a minified
-    // one are a texel apart on the finer level -- half a texel on the coarser, whose adds stay as they were)
-    int run_cell = -1;
-    T run_w[4] = {T(0), T(0), T(0), T(0)};
-    auto emit_run = [&](int l, const T (&g)[4]) {
-      if (run_cell < 0) return;
-      double* wp = s_win + slot_base(l) + run_cell;
-      const int stride = slot_stride(l), chan = slot_chan(l);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        if (c >= C) break;
-        lds_add(wp + c * chan, static_cast<double>(run_w[0] * g[c]));
-        lds_add(wp + c * chan + 1, static_cast<double>(run_w[1] * g[c]));
-        lds_add(wp + c * chan + stride, static_cast<double>(run_w[2] * g[c]));
-        lds_add(wp + c * chan + stride + 1, static_cast<double>(run_w[3] * g[c]));
-      }
-      run_cell = -1;
-    };
-    for (int i = 0; (live[0] || live[1]) && i < t.n && !DRTK_DBG(dbg, 32); ++i) {
-      T x, y;
-      tap_xy(i, x, y);
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        if (!live[s]) continue;
-        const int d = t.d1 + s;
-        const int h = lv_h[s], w = lv_w[s];
-        const int64_t plane = lv_h[s] * lv_w[s]; // < 2^31, checked by fill_table()
-        const GlobalPtr<const T> inp = lv_inp[s];
-        const T alpha = s == 0 ? alpha_2 : alpha_1;
-        const Quad<T> q = bilinear_quad<T>(x, y, h, w, padding, align_corners);
-        const int ix_se = q.ix_nw + 1, iy_se = q.iy_nw + 1;
-        // window cell of the north-west corner (the other three are +1 in x / y), or -1 if not windowed
-        const int l = d - ref;
-        const int cell = slot_cell(l, q.ix_nw, q.iy_nw);
-        const int stride = slot_stride(l), chan = slot_chan(l);
-        T g[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) g[c] = c < C ? go[c] * alpha : T(0);
-        T gix = T(0), giy = T(0);
-        // Interior taps -- all four corners inside the level, i.e. nearly all of them -- take a straight-line path: the
-        // per-corner validity tests of the general form below each cost a divergent branch (the general form compiled to
-        // 234 exec-mask regions), while here a tap is 2C 8-byte texel loads, 4C adds and the grid-gradient products with no
-        // branch but window / fallback.  A channel whose weighted gradient is zero adds +-0 (the general form skips it).
-        if ((q.o_nw | q.o_ne | q.o_sw | q.o_se) >= 0) {
-          Pair<T> top[4], bot[4];
-#pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            top[c] = bot[c] = Pair<T>{T(0), T(0)};
-            if (c < C && !DRTK_DBG(dbg, 2)) {
-              top[c] = *(GlobalPtr<const Pair<T>>)(inp + c * plane + q.o_nw);
-              bot[c] = *(GlobalPtr<const Pair<T>>)(inp + c * plane + q.o_sw);
-            }
-          }
-          if (DRTK_DBG(dbg, 1)) {
-          } else if (cell >= 0) {
-            // the taps of a pixel that land in the SAME 2 x 2 cell of a level -- on a magnified texture nearly all of
-            // them -- are merged before they touch LDS: their corner weights add up in registers and the cell gets one
-            // set of adds when the run ends (a different cell, or the last tap)
-            if (s == 1) {
-              double* wp = s_win + slot_base(l) + cell;
-#pragma unroll
-              for (int c = 0; c < 4; ++c) {
-                if (c >= C) break;
-                lds_add(wp + c * chan, static_cast<double>(q.nw * g[c]));
-                lds_add(wp + c * chan + 1, static_cast<double>(q.ne * g[c]));
-                lds_add(wp + c * chan + stride, static_cast<double>(q.sw * g[c]));
-                lds_add(wp + c * chan + stride + 1, static_cast<double>(q.se * g[c]));
-              }
-            } else if (cell != run_cell) {
-              emit_run(l, g);
-              run_cell = cell;
-              run_w[0] = q.nw, run_w[1] = q.ne, run_w[2] = q.sw, run_w[3] = q.se;
-            } else {
-              run_w[0] += q.nw, run_w[1] += q.ne, run_w[2] += q.sw, run_w[3] += q.se;
-            }
-          } else if (i < 16) {
-            pending |= 1u << (2 * i + s);
-          } else {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-              if (c >= C) break;
-              const GlobalPtr<T> gp = grad_base(d, plane) + c * plane;
-              atomic_add_g1(gp + q.o_nw, q.nw * g[c]);
-              atomic_add_g1(gp + q.o_ne, q.ne * g[c]);
-              atomic_add_g1(gp + q.o_sw, q.sw * g[c]);
-              atomic_add_g1(gp + q.o_se, q.se * g[c]);
-            }
-          }
-          const T fy1 = iy_se - q.iy, fy0 = q.iy - q.iy_nw, fx1 = ix_se - q.ix, fx0 = q.ix - q.ix_nw;
-#pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            if (c >= C || DRTK_DBG(dbg, 16)) break;
-            const T gOut = g[c];
-            // with a zero upstream gradient every term is +-0 * finite: the texels count as 0
-            const T v_nw = gOut != T(0) ? top[c].x : T(0), v_ne = gOut != T(0) ? top[c].y : T(0);
-            const T v_sw = gOut != T(0) ? bot[c].x : T(0), v_se = gOut != T(0) ? bot[c].y : T(0);
-            gix -= v_nw * fy1 * gOut;
-            giy -= v_nw * fx1 * gOut;
-            gix += v_ne * fy1 * gOut;
-            giy -= v_ne * fx0 * gOut;
-            gix -= v_sw * fy0 * gOut;
-            giy += v_sw * fx1 * gOut;
-            gix += v_se * fy0 * gOut;
-            giy += v_se * fx0 * gOut;
-          }
-        } else {
-        // General form (a tap on the border of its level: rare), one channel at a time -- nothing of it is live across the
-        // interior path above
-        const bool defer = !DRTK_DBG(dbg, 1) && cell < 0 && i < 16 && (q.o_nw & q.o_ne & q.o_sw & q.o_se) != -1; // (all four corners outside the level: nothing to add anywhere)
-        if (defer) pending |= 1u << (2 * i + s);
-#pragma unroll 1
-        for (int c = 0; c < C; ++c) {
-          const T gOut = c == 0 ? g[0] : c == 1 ? g[1] : c == 2 ? g[2] : g[3];
-          if (gOut == T(0)) continue; // a zero upstream gradient (masked channel) adds nothing; its texels count as 0
-          const GlobalPtr<const T> p = inp + c * plane;
-          T v_nw = T(0), v_ne = T(0), v_sw = T(0), v_se = T(0);
-          if (!DRTK_DBG(dbg, 2)) {
-            if (q.o_nw >= 0) v_nw = p[q.o_nw];
-            if (q.o_ne >= 0) v_ne = p[q.o_ne];
-            if (q.o_sw >= 0) v_sw = p[q.o_sw];
-            if (q.o_se >= 0) v_se = p[q.o_se];
-          }
-          if (!DRTK_DBG(dbg, 1)) {
-            if (cell >= 0) {
-              double* wp = s_win + slot_base(l) + c * chan + cell;
-              if (q.o_nw >= 0) lds_add(wp, static_cast<double>(q.nw * gOut));
-              if (q.o_ne >= 0) lds_add(wp + 1, static_cast<double>(q.ne * gOut));
-              if (q.o_sw >= 0) lds_add(wp + stride, static_cast<double>(q.sw * gOut));
-              if (q.o_se >= 0) lds_add(wp + stride + 1, static_cast<double>(q.se * gOut));
-            } else if (!defer) {
-              const GlobalPtr<T> gp = grad_base(d, plane) + c * plane;
-              if (q.o_nw >= 0) atomic_add_g1(gp + q.o_nw, q.nw * gOut);
-              if (q.o_ne >= 0) atomic_add_g1(gp + q.o_ne, q.ne * gOut);
-              if (q.o_sw >= 0) atomic_add_g1(gp + q.o_sw, q.sw * gOut);
-              if (q.o_se >= 0) atomic_add_g1(gp + q.o_se, q.se * gOut);
-            }
-          }
-          if (q.o_nw >= 0) {
-            gix -= v_nw * (iy_se - q.iy) * gOut;
-            giy -= v_nw * (ix_se - q.ix) * gOut;
-          }
-          if (q.o_ne >= 0) {
-            gix += v_ne * (iy_se - q.iy) * gOut;
-            giy -= v_ne * (q.ix - q.ix_nw) * gOut;
-          }
-          if (q.o_sw >= 0) {
-            gix -= v_sw * (q.iy - q.iy_nw) * gOut;
-            giy += v_sw * (ix_se - q.ix) * gOut;
-          }
-          if (q.o_se >= 0) {
-            gix += v_se * (q.iy - q.iy_nw) * gOut;
-            giy += v_se * (q.ix - q.ix_nw) * gOut;
-          }
-        }
-        } // general form
-        acc_x += q.mx * gix;
-        acc_y += q.my * giy;
-      }
-    }
-    // the last run
-    if (live[0]) {
-      T g[4];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) g[c] = c < C ? go[c] * alpha_2 : T(0);
-      emit_run(t.d1 - ref, g);
-    }
-    store_grid_grad<T>(grad_grid, ggl, n, pix, acc_x, acc_y);
-    DRTK_MIP_STAT(8, (live[0] ? t.n : 0) + (live[1] ? t.n : 0));
-    DRTK_MIP_STAT(9, __popc(pending));
-  }
-  if (tid == 0) DRTK_MIP_STAT(0, 1);
-  __syncthreads();
-  // flush the windows: consecutive threads = consecutive texels of a row; cells that stayed 0 cost nothing,
-  // cells outside the level were never written (only in-bounds corners are accumulated).  With `rearm` the cells are
-  // zeroed as they are read: the windows serve a second round.
-  auto flush = [&](int ref_level, bool rearm) {
-#pragma unroll
-    for (int l = 0; l < kWinLevels; ++l) {
-      const int d = ref_level + l;
-      if (d >= mipmaps || wox[l] == INT32_MAX || DRTK_DBG(dbg, 4)) continue;
-      const int h = s_h[d], w = s_w[d];
-      const int64_t plane = int64_t(h) * w;
-      const GlobalPtr<T> ginp = (GlobalPtr<T>)(static_cast<T*>(s_grad[d]) + int64_t(n) * C * plane);
-      for (int c = 0; c < C; ++c) {
-        // ONE cell per lane: an atomic instruction's lanes are consecutive texels of a row, one request per 64-byte line
-        // (two cells per lane asked for every line twice -- see mipmap_backward_lean_kernel's flush)
-        const int stride = 1 << wsx[l], chan = wcells[l];
-        double* win1 = s_win + (l == 0 ? 0 : C * wcells[0]) + c * chan;
-        for (int i = tid; i < win_rows[l] * stride; i += kMipBlock) { // rows beyond win_rows were never written
-          const double q = win1[i];
-          if (q != 0.0) {
-            if (rearm) win1[i] = 0.0;
-            const int gx = wox[l] + (i & (stride - 1)), gy = woy[l] + (i >> wsx[l]);
-            atomic_add_g1(ginp + c * plane + int64_t(gy) * w + gx, static_cast<T>(q));
-          }
-        }
-      }
-    }
-  };
-  // Does any pixel of the tile have taps the windows did not hold?  (16 % of the tiles of the minified benchmark scenes;
-  // on the textured benchmark the atlas seam -- neighbouring pixels sample opposite ends of the texture -- and the limb,
-  // where eight anisotropic taps spread over more texels than a window is wide.)  `pending` says which.
-#ifndef DRTK_MIP_ROUNDS
-#define DRTK_MIP_ROUNDS 6 // same-box A/B (textured benchmark / kernel_bench at 1 texel per pixel / at 4): 1 round (all misses to
-#endif                    // global memory, rounds 1-2) 2.15 / 4.58 / 11.7 ms; 2: 2.00 / 3.80 / 9.85; 3: 1.95 / 3.41 / 9.10; 4: 1.94 / 3.11 / 8.63; 6: 1.97 / 2.97 / 8.09
-  // ---- further rounds: the windows are moved onto the taps that are still pending and those taps alone are accumulated
-  // (texture gradient only: the grid gradient is complete).  What is still pending after the last round -- a region of
-  // the texture or a level too many -- goes to global memory corner by corner, as all misses did before.
-  // HOPELESS tiles (round 5): where a round catches only a handful of (tap, level) pairs, the taps are scattered beyond what
-  // windows can hold -- the poles of an atlas, where neighbouring pixels sample texels thousands of columns apart: on the
-  // textured benchmark 1.7 % of the tiles ran all five further rounds and still sent nearly all of their taps to global
-  // memory afterwards (profiles/mipmap_bench.py --rounds-stats), 39 % of all tile-rounds.  The round after such a round is
-  // the tile's last (what is pending goes to global memory at once).  The test is on PAIRS caught, not on a share: a tile
-  // of a minified texture needs many windows and every one of its rounds catches hundreds of pairs -- cutting those short
-  // (a first version tested the share of pixels that still had pending taps) cost 11 % on the minified scenes.
-  // Same-box A/B of the threshold (textured benchmark / kernel_bench at 1 and 4 texels per pixel, ms): off 1.565 / 2.755 /
-  // 7.74; 32 pairs 1.565 / 2.80 / 7.94; 96 1.56 / 2.98 / 8.23; 256 1.538 / 3.03 / 8.50 -- what the pole tiles save, the
-  // tiles of a minified texture lose several times over: the switch stays off.
-  int ref_now = ref, npend_before = 0;
-  for (int round = 1;; ++round) {
-    const bool again = __syncthreads_or(pending != 0) && !DRTK_DBG(dbg, 8);
-    flush(ref_now, again);
-    if (!again) return;
-    if (tid == 0) DRTK_MIP_STAT(round < 7 ? round : 7, 1);
-    bool last = round >= DRTK_MIP_ROUNDS - 1; // (or hopeless, below)
-    __syncthreads(); // everybody has finished its flush (it reads the origins)
-    if (tid == 0) s_ref = kMaxLevels, s_npend = 0;
-    if (tid < kWinLevels) s_ox[tid] = s_oy[tid] = INT32_MAX, s_hx[tid] = s_hy[tid] = INT32_MIN;
-    // where this pixel's pending taps are: bounding box of their north-west texels per level
-    bool miss[2] = {false, false};
-    int miss_x[2] = {INT32_MAX, INT32_MAX}, miss_y[2] = {INT32_MAX, INT32_MAX}, miss_hx[2] = {INT32_MIN, INT32_MIN}, miss_hy[2] = {INT32_MIN, INT32_MIN};
-    for (uint32_t todo = pending; todo;) {
-      const int bit = __builtin_ctz(todo);
-      todo &= todo - 1;
-      const int i = bit >> 1, s2 = bit & 1;
-      T x, y;
-      tap_xy(i, x, y);
-      const int d = t.d1 + s2;
-      const Quad<T> q = bilinear_quad<T>(x, y, s_h[d], s_w[d], padding, align_corners);
-      if (s2 == 0) {
-        miss[0] = true, miss_x[0] = min(miss_x[0], q.ix_nw), miss_y[0] = min(miss_y[0], q.iy_nw);
-        miss_hx[0] = max(miss_hx[0], q.ix_nw), miss_hy[0] = max(miss_hy[0], q.iy_nw);
-      } else {
-        miss[1] = true, miss_x[1] = min(miss_x[1], q.ix_nw), miss_y[1] = min(miss_y[1], q.iy_nw);
-        miss_hx[1] = max(miss_hx[1], q.ix_nw), miss_hy[1] = max(miss_hy[1], q.iy_nw);
-      }
-    }
-    __syncthreads();
-    {
-      const int d_min = wave_min_i32(miss[0] ? t.d1 : miss[1] ? t.d1 + 1 : kMaxLevels);
-      // the tile's pending (tap, level) pairs: a wave's count from five ballots over the bits of its lanes' counts (<= 32)
-      const int pc = __popc(pending);
-      int wave_pc = 0;
-#pragma unroll
-      for (int b = 0; b < 6; ++b) wave_pc += __popcll(__ballot((pc >> b) & 1)) << b;
-      if ((tid & (kWave - 1)) == 0) {
-        atomicMin(&s_ref, d_min);
-        atomicAdd(&s_npend, wave_pc);
-      }
-    }
-    __syncthreads();
-    ref_now = s_ref;
-    {
-      // HOPELESS: the round before this one caught fewer than kHopelessPairs pairs -- scattered taps; this round is the last
-      const int npend = s_npend;
-      const bool hopeless = DRTK_MIP_HOPELESS && round >= 2 && npend_before - npend < DRTK_MIP_HOPELESS_PAIRS;
-      if (tid == 0 && hopeless) DRTK_MIP_STAT(11, 1);
-      npend_before = npend;
-      last = last || hopeless;
-    }
-    {
-      int lo_x[kWinLevels], lo_y[kWinLevels], hi_x[kWinLevels], hi_y[kWinLevels];
-#pragma unroll
-      for (int l = 0; l < kWinLevels; ++l) lo_x[l] = lo_y[l] = INT32_MAX, hi_x[l] = hi_y[l] = INT32_MIN;
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        const int l = t.d1 + s2 - ref_now;
-#pragma unroll
-        for (int k = 0; k < kWinLevels; ++k) {
-          if (miss[s2] && k == l) {
-            lo_x[k] = min(lo_x[k], miss_x[s2]), lo_y[k] = min(lo_y[k], miss_y[s2]);
-            hi_x[k] = max(hi_x[k], miss_hx[s2]), hi_y[k] = max(hi_y[k], miss_hy[s2]);
-          }
-        }
-      }
-#pragma unroll
-      for (int l = 0; l < kWinLevels; ++l) {
-        const int a = wave_min_i32(lo_x[l]), b = wave_min_i32(lo_y[l]);
-        const int g = wave_max_i32(hi_x[l]), e = wave_max_i32(hi_y[l]);
-        if ((tid & (kWave - 1)) == 0 && a != INT32_MAX) {
-          atomicMin(&s_ox[l], a);
-          atomicMin(&s_oy[l], b);
-          atomicMax(&s_hx[l], g);
-          atomicMax(&s_hy[l], e);
-        }
-      }
-    }
-    __syncthreads();
-    {
-      int lox[kWinLevels], loy[kWinLevels], hix[kWinLevels], hiy[kWinLevels];
-#pragma unroll
-      for (int l = 0; l < kWinLevels; ++l) {
-        lox[l] = __builtin_amdgcn_readfirstlane(s_ox[l]), loy[l] = __builtin_amdgcn_readfirstlane(s_oy[l]);
-        hix[l] = __builtin_amdgcn_readfirstlane(s_hx[l]), hiy[l] = __builtin_amdgcn_readfirstlane(s_hy[l]);
-      }
-      // (slot 0 always has pending taps: ref_now is the finest level that has any.  The boxes are those of the pending
-      // taps' true north-west texels -- whatever the padding mode -- and only pending taps are accumulated in a round, so
-      // the flush may stop at the box's last row)
-      shape_slots(lox, loy, hix, hiy, false);
-    }
-    if (pending != 0) {
-      uint32_t todo = pending;
-      while (todo) {
-        const int bit = __builtin_ctz(todo);
-        todo &= todo - 1;
-        const int i = bit >> 1, s2 = bit & 1;
-        T x, y;
-        tap_xy(i, x, y);
-        const int d = t.d1 + s2;
-        const int h = s_h[d], w = s_w[d];
-        const int64_t plane = int64_t(h) * w;
-        const T alpha = s2 == 0 ? alpha_2 : alpha_1;
-        const Quad<T> q = bilinear_quad<T>(x, y, h, w, padding, align_corners);
-        const int l = d - ref_now;
-        const int cell = slot_cell(l, q.ix_nw, q.iy_nw);
-        const int stride = slot_stride(l), chan = slot_chan(l);
-        if (cell < 0 && !last) continue; // stays pending: the next round's windows
-        pending &= ~(1u << bit);
-        if (cell < 0) DRTK_MIP_STAT(10, 1);
-        const GlobalPtr<T> ginp = (GlobalPtr<T>)(static_cast<T*>(s_grad[d]) + int64_t(n) * C * plane);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          if (c >= C) break;
-          const T gc = go[c] * alpha;
-          if (gc == T(0)) continue;
-          if (cell >= 0) {
-            double* wp = s_win + slot_base(l) + c * chan + cell;
-            if (q.o_nw >= 0) lds_add(wp, static_cast<double>(q.nw * gc));
-            if (q.o_ne >= 0) lds_add(wp + 1, static_cast<double>(q.ne * gc));
-            if (q.o_sw >= 0) lds_add(wp + stride, static_cast<double>(q.sw * gc));
-            if (q.o_se >= 0) lds_add(wp + stride + 1, static_cast<double>(q.se * gc));
-          } else {
-            const GlobalPtr<T> gp = ginp + c * plane;
-            if (q.o_nw >= 0) atomic_add_g1(gp + q.o_nw, q.nw * gc);
-            if (q.o_ne >= 0) atomic_add_g1(gp + q.o_ne, q.ne * gc);
-            if (q.o_sw >= 0) atomic_add_g1(gp + q.o_sw, q.sw * gc);
-            if (q.o_se >= 0) atomic_add_g1(gp + q.o_se, q.se * gc);
-          }
-        }
-      }
-    }
-  }
-}
-
-// ---- Backward, bilinear, any padding, any C, float and double: the tile kernel with the LEAN tap loop (round 5; reflection
-// and double: round 6) ----------------------------------------------------------------------------------------------------
-// mipmap_backward_tiled2_kernel's placement, shaped window slots, rounds and flush, with the tap loop rewritten the way
-// the lean forward was (one straight line per (tap, level) for the whole wave: no Quad, no per-corner logic, regrouped
-// products, texture channels a template parameter) -- for the instructions, and for the REGISTERS: the tile kernels sat at
-// 151-168 VGPRs = 3 waves per SIMD with every tile's chain (loads -> barrier -> placement -> barrier -> taps -> barrier ->
-// flush) exposed; at <= 128 a CU holds four tiles instead of three.
+constexpr int kWinLevels = 2; // window slots: the tile's finest live level and the next one
 // Wider textures (C > 4: neural textures) run it once per block of four channels (`C_total`, `c0`; the grid gradient
-// accumulates over the blocks, the tap geometry is recomputed per block) instead of the wave-private kernel below.
+// accumulates over the blocks, the tap geometry is recomputed per block).
 // Tiles per CU (= waves per SIMD), up to three channels: FIVE since late round 5 -- 94-96 registers (the pixel's index is
 // rebuilt where it is needed instead of being carried: it was what spilled) and windows of 2 x 512 accumulators per channel
 // (24.5 KB for RGB).  Same-box A/B, ms (textured benchmark 2 x 4096^2 / 8 x 2048^2 / kernel_bench's minified scenes at 1 and 4
@@ -1688,7 +1074,7 @@ __global__ __launch_bounds__(kMipBlock, sizeof(T) == 8 ? DRTK_MIP_T3_OCC_F64 : P
   // (tap, level) pairs that find no window cell in this round: not sent to global memory one corner and channel at a
   // time -- scattered float atomics of single lanes, 0.72 of this kernel's 2.2 ms on the textured benchmark although
   // only a few per cent of the taps miss -- but remembered (per level of the pixel: did any tap miss, and where) for a
-  // further round with the windows moved onto them (below, up to DRTK_MIP_ROUNDS rounds).
+  // further round with the windows moved onto them (below, up to DRTK_MIP_LEAN_ROUNDS rounds).
   // (where they missed is NOT carried through the tap loop -- six registers at its bound: a round recomputes the
   // north-west texels of its pending taps, which it walks anyway)
   uint32_t pending = 0; // bit 2 i + s: tap i on the pixel's level s found no window cell yet (taps >= 16 are never deferred)
@@ -1792,7 +1178,7 @@ __global__ __launch_bounds__(kMipBlock, sizeof(T) == 8 ? DRTK_MIP_T3_OCC_F64 : P
           }
         }
         // ---- grid gradient: texels of the (interior) tap; d/dx of the bilinear form = differences of texels
-        const int plane = w * h; // <= kLeanMaxPlane (the dispatch): c * plane + offset fits 32 bits
+        const int plane = w * h; // <= kMaxPlane32 (the dispatch): c * plane + offset fits 32 bits
         const GlobalPtr<const T> inp = (GlobalPtr<const T>)(static_cast<const T*>(s_ptr[d]) + int64_t(n) * s_sn[d]) + int64_t(c0) * plane;
         // (round 6: the loads run under `interior`, one exec-mask region -- the lanes without an interior tap used to load the
         // pair at offset 0 of their level: on a 1 x 1 level, one element beyond the last channel of the last view.  What
@@ -1857,7 +1243,7 @@ __global__ __launch_bounds__(kMipBlock, sizeof(T) == 8 ? DRTK_MIP_T3_OCC_F64 : P
                 }
               }
               if (interior) continue; // (its grid gradient is in the straight line above)
-              const GlobalPtr<const T> pch = inp + c * plane; // (c <= 3, plane <= kLeanMaxPlane)
+              const GlobalPtr<const T> pch = inp + c * plane; // (c <= 3, plane <= kMaxPlane32)
               T v_nw = T(0), v_ne = T(0), v_sw = T(0), v_se = T(0);
               if (!DRTK_DBG(dbg, 2)) {
                 if (q.o_nw >= 0) v_nw = pch[q.o_nw];
@@ -2258,27 +1644,25 @@ __global__ __launch_bounds__(kMipBlock, sizeof(T) == 8 ? DRTK_MIP_T3_OCC_F64 : P
   }
 }
 
-// ---- Backward, bilinear, f32, any C: WAVE-PRIVATE windows (round 4) -------------------------------------------------
-// Round 4's tile kernel was bound by its chain of dependent round trips at 3 waves per SIMD: 48 KB of
-// workgroup-shared windows and 157 VGPRs hold the occupancy there, and every phase of a tile (window placement, taps,
-// flush, each further round) is fenced by workgroup barriers -- 0.85 of its 1.95 ms remain with no accumulation at all
-// (profiles/r03/mipmap_pmc_sq.txt).  Here a WAVE owns its 16 x 4 pixels and a window of its own:
+// ---- Backward, bicubic, any C, float and double: WAVE-PRIVATE 4 x 4 windows (round 4; rows and three waves: round 6) -------
+// A WAVE owns its 16 x 4 pixels of the tile and a window of its own (mipmap_grid_sampler_kernel.cu:806-861 is the footprint):
 //   * no workgroup barrier after the level table is staged: placement, taps, flush and the further rounds of a wave are
 //     ordered by the wave's own LDS counter, so 20+ independent waves per CU overlap each other's round trips;
 //   * kWaveCells cells per channel (double accumulators, ds_add_f64) shaped like the bounding box of the wave's taps --
-//     2 KB per channel and wave instead of 16 KB per channel and workgroup; channels go in blocks of four, so any C runs
-//     here (the level pair, tap geometry and grid gradient of a pixel are per block; the reference's sums regrouped);
+//     2 KB per channel and wave; channels go in blocks of four, so any C runs here (the level pair, tap geometry and grid
+//     gradient of a pixel are per block; the reference's sums regrouped);
 //   * per-level sizes and pointers are re-read from the LDS table inside the tap loop instead of being carried in
-//     registers; taps that touch the border of a level (not all four corners inside) go straight to global memory.
-// Taps that find no cell stay pending and get the window in a further round, exactly as in the tiled kernel.
+//     registers; a tap spans four cells per axis; interior footprints (sixteen consecutive texels inside the level) are
+//     windowed, the others go corner by corner straight to global memory.
+// Taps that find no cell stay pending and get the window in a further round, as in the lean tile kernel.
+// (Before round 4 bicubic took the direct kernel, sixteen global float atomics per tap, level and channel: 89 ms against
+// 1.96 ms bilinear on the textured benchmark.  Round 4 also ran BILINEAR calls here: slower than the tile kernel at C = 3,
+// 2.52 against 1.95 ms, and replaced for wider textures by the lean kernel's passes of four channels in round 5.)
 #ifndef DRTK_MIP_WAVE_CELLS
 #define DRTK_MIP_WAVE_CELLS 256
 #endif
 constexpr int kWaveCells = DRTK_MIP_WAVE_CELLS; // window cells per channel and wave, both levels together
 constexpr int kWaveWinW = 32;                   // widest window row (the flush walks two rows of <= 32 cells per step)
-#ifndef DRTK_MIP_WAVE_OCC
-#define DRTK_MIP_WAVE_OCC 3
-#endif
 
 #ifndef DRTK_BICUBIC_COMPACT_SLOW
 #define DRTK_BICUBIC_COMPACT_SLOW 1
@@ -2289,16 +1673,14 @@ constexpr int kWaveWinW = 32;                   // widest window row (the flush 
 #ifndef DRTK_MIP_BICUBIC_OCC
 #define DRTK_MIP_BICUBIC_OCC 3 // (round 6: the compact border path fits 168 registers; 2 until then)
 #endif
-// MODE 0: bilinear (2 x 2 texels per tap); MODE 2: bicubic (4 x 4: mipmap_grid_sampler_kernel.cu:806-861) -- the same windows with
-// a span of four cells, interior taps (sixteen consecutive texels inside the level) windowed, the others corner by corner.
-template <typename T, int PAD, bool ALIGN, int MODE = 0>
-__global__ __launch_bounds__(kMipBlock, sizeof(T) == 8 ? 1 : (MODE == 2 ? DRTK_MIP_BICUBIC_OCC : DRTK_MIP_WAVE_OCC)) void mipmap_backward_wave_kernel(
+template <typename T, int PAD, bool ALIGN>
+__global__ __launch_bounds__(kMipBlock, sizeof(T) == 8 ? 1 : DRTK_MIP_BICUBIC_OCC) void mipmap_backward_wave_kernel(
     LevelTable lv, int mipmaps, const T* __restrict__ grad_out, const T* __restrict__ grid, GridLayout gl,
     const T* __restrict__ vt, int H, int W, int C, int tiles_x, int max_aniso,
     bool force_max_aniso, bool clip_grad, T* __restrict__ grad_grid, GridLayout ggl, int strip, int dbg) {
   constexpr int padding = PAD;
   constexpr bool align_corners = ALIGN;
-  constexpr int kSpan = MODE == 2 ? 4 : 2; // cells per tap and axis
+  constexpr int kSpan = 4; // cells per tap and axis
   static_assert(kTileW == 16 && kWave == 64, "a wave covers 16 x 4 pixels");
   __shared__ double s_f[kTapTab * kTapTab];
   __shared__ const void* s_ptr[kMaxLevels];
@@ -2333,11 +1715,11 @@ __global__ __launch_bounds__(kMipBlock, sizeof(T) == 8 ? 1 : (MODE == 2 ? DRTK_M
     x = t.u + static_cast<T>(t.du * f);
     y = t.v + static_cast<T>(t.dv * f);
   };
-  auto texel_floor = [&](T coord, int size) -> int { // (as in the tiled kernel: any origin is correct)
+  auto texel_floor = [&](T coord, int size) -> int { // (any origin is correct)
     T unused;
     const T c = unnormalize(coord, size, align_corners, &unused);
     const T lo = padding == 0 ? T(-1) : T(0);
-    return static_cast<int>(floor(fmin(fmax(c, lo), static_cast<T>(size - 1)))) - (MODE == 2 ? 1 : 0);
+    return static_cast<int>(floor(fmin(fmax(c, lo), static_cast<T>(size - 1)))) - 1;
   };
 
   for (int c0 = 0; c0 < C; c0 += kChBlock) {
@@ -2478,215 +1860,110 @@ __global__ __launch_bounds__(kMipBlock, sizeof(T) == 8 ? 1 : (MODE == 2 ? DRTK_M
           if (!live[s]) continue;
           const int d = t.d1 + s;
           const int h = s_h[d], w = s_w[d];
-          const int plane = h * w; // < 2^31, checked by fill_table()
+          const int plane = h * w; // <= kMaxPlane32 (the dispatch): c * plane + offset fits 32 bits for c <= 3
           const GlobalPtr<const T> inp = (GlobalPtr<const T>)(static_cast<const T*>(s_ptr[d]) + int64_t(n) * s_sn[d]) + int64_t(c0) * plane;
           const T alpha = s == 0 ? alpha_2 : alpha_1;
-          if constexpr (MODE == 2) {
-            const Cubic<T> cb = bicubic_footprint<T>(x, y, h, w, padding, align_corners);
-            T xc[4], yc[4], xg[4], yg[4];
-            cubic_coeffs(xc, cb.tx);
-            cubic_coeffs(yc, cb.ty);
-            cubic_coeffs_grad(xg, cb.tx);
-            cubic_coeffs_grad(yg, cb.ty);
-            const GlobalPtr<T> gp = (GlobalPtr<T>)(static_cast<T*>(s_grad[d]) + (int64_t(n) * C + c0) * plane);
-            T gix = T(0), giy = T(0);
-            const int bx = cb.xi[0], by = cb.yi[0];
-            const bool interior = bx >= 0 && by >= 0 && cb.xi[1] == bx + 1 && cb.xi[2] == bx + 2 && cb.xi[3] == bx + 3 &&
-                cb.yi[1] == by + 1 && cb.yi[2] == by + 2 && cb.yi[3] == by + 3;
-            int stride = 0;
-            const int cell = interior ? cell_of(d, bx, by, stride) : -1;
-            const bool defer = interior && cell < 0 && i < 16 && !DRTK_DBG(dbg, 1);
-            if (defer) {
-              pending |= 1u << (2 * i + s);
-              note_miss(s, bx, by);
-            }
-#pragma unroll 1
-            for (int c = 0; c < cc; ++c) {
-              const T gOut = go[c] * alpha;
-              if (gOut == T(0)) continue; // every term below would be +-0 * finite
-              const GlobalPtr<const T> pc = inp + c * plane;
-              if (DRTK_BICUBIC_ROWS && sizeof(T) == 4 && interior && !DRTK_DBG(dbg, 2)) { // (double: 12 registers spilled with the rows in flight)
-                // Round 6: the sixteen texels of an interior footprint as FOUR 16-byte row loads (element-aligned), like the
-                // forward -- they were sixteen predicated 4-byte loads, each in its own exec-mask region with its own wait
-                // (6.87 ms for RGB on the textured benchmark's inputs against 1.29 bilinear).  Same products, same order.
-                typedef T Quad4 __attribute__((ext_vector_type(4), aligned(sizeof(T))));
-                Quad4 row[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) row[r] = *(GlobalPtr<const Quad4>)(pc + (by + r) * w + bx);
-                // ... and ROW BY ROW: the footprint's weights are an outer product xc (x) yc, so a row's four cells share
-                // gOut yc[j] and the grid gradient is  -gOut sum_j yc[j] (row_j . xg)  /  -gOut sum_j yg[j] (row_j . xc): 8
-                // multiply-adds per row instead of six operations per cell with their 48 hoisted coefficient products
-                // (the registers that held the kernel at two waves per SIMD)
-#pragma unroll
-                for (int j2 = 0; j2 < 4; ++j2) {
-                  const T gy = gOut * yc[j2];
-                  if (DRTK_DBG(dbg, 1)) {
-                  } else if (cell >= 0) {
-                    double* wp = win + cell + c * kWaveCells + j2 * stride;
-#pragma unroll
-                    for (int i2 = 0; i2 < 4; ++i2) lds_add(wp + i2, static_cast<double>(gy * xc[i2]));
-                  } else if (!defer) {
-                    const GlobalPtr<T> gq = gp + c * plane + ((by + j2) * w + bx);
-#pragma unroll
-                    for (int i2 = 0; i2 < 4; ++i2) atomic_add_g1(gq + i2, gy * xc[i2]);
-                  }
-                  const T sx = row[j2].x * xg[0] + row[j2].y * xg[1] + row[j2].z * xg[2] + row[j2].w * xg[3];
-                  const T sc = row[j2].x * xc[0] + row[j2].y * xc[1] + row[j2].z * xc[2] + row[j2].w * xc[3];
-                  gix -= gy * sx;
-                  giy -= (gOut * yg[j2]) * sc;
-                }
-                continue;
-              }
-              if constexpr (DRTK_BICUBIC_COMPACT_SLOW && sizeof(T) == 4) {
-                // a footprint that touches the border of its level (rare): the sixteen cells in a loop that is NOT unrolled,
-                // coefficients and indices picked by selects -- the unrolled form below (sixteen predicated loads and their
-                // products in flight) is what kept this kernel at 225-243 registers = two waves per SIMD
-                auto sel4 = [](const auto (&a)[4], int k) { return k == 0 ? a[0] : k == 1 ? a[1] : k == 2 ? a[2] : a[3]; };
-#pragma unroll 1
-                for (int e = 0; e < 16; ++e) {
-                  const int i2 = e >> 2, j2 = e & 3;
-                  const int xi = sel4(cb.xi, i2), yi = sel4(cb.yi, j2);
-                  const bool ok = xi >= 0 && yi >= 0;
-                  const int o = ok ? yi * w + xi : 0;
-                  const T cxw = sel4(xc, i2), cyw = sel4(yc, j2);
-                  const T wgt = gOut * cxw * cyw;
-                  if (DRTK_DBG(dbg, 1)) {
-                  } else if (cell >= 0) { // (an interior footprint whose rows were not taken above: the ablation build only)
-                    lds_add(win + cell + c * kWaveCells + j2 * stride + i2, static_cast<double>(wgt));
-                  } else if (ok && !defer) {
-                    atomic_add_g1(gp + c * plane + o, wgt);
-                  }
-                  const T val = (ok && !DRTK_DBG(dbg, 2)) ? pc[o] : T(0);
-                  gix -= gOut * val * (sel4(xg, i2) * cyw);
-                  giy -= gOut * val * (sel4(yg, j2) * cxw);
-                }
-                continue;
-              }
-#pragma unroll
-              for (int i2 = 0; i2 < 4; ++i2) {
-#pragma unroll
-                for (int j2 = 0; j2 < 4; ++j2) {
-                  const bool ok = cb.xi[i2] >= 0 && cb.yi[j2] >= 0;
-                  const int o = ok ? cb.yi[j2] * w + cb.xi[i2] : 0;
-                  const T wgt = gOut * xc[i2] * yc[j2];
-                  if (DRTK_DBG(dbg, 1)) {
-                  } else if (cell >= 0) {
-                    lds_add(win + cell + c * kWaveCells + j2 * stride + i2, static_cast<double>(wgt));
-                  } else if (ok && !defer) {
-                    atomic_add_g1(gp + c * plane + o, wgt);
-                  }
-                  const T val = (ok && !DRTK_DBG(dbg, 2)) ? pc[o] : T(0);
-                  gix -= gOut * val * (xg[i2] * yc[j2]);
-                  giy -= gOut * val * (yg[j2] * xc[i2]);
-                }
-              }
-            }
-            acc_x += cb.mx * gix;
-            acc_y += cb.my * giy;
-            continue;
-          }
-          const Quad<T> q = bilinear_quad<T>(x, y, h, w, padding, align_corners);
-          const int ix_se = q.ix_nw + 1, iy_se = q.iy_nw + 1;
-          T g[kChBlock];
-#pragma unroll
-          for (int c = 0; c < kChBlock; ++c) g[c] = c < cc ? go[c] * alpha : T(0);
+          const Cubic<T> cb = bicubic_footprint<T>(x, y, h, w, padding, align_corners);
+          T xc[4], yc[4], xg[4], yg[4];
+          cubic_coeffs(xc, cb.tx);
+          cubic_coeffs(yc, cb.ty);
+          cubic_coeffs_grad(xg, cb.tx);
+          cubic_coeffs_grad(yg, cb.ty);
+          const GlobalPtr<T> gp = (GlobalPtr<T>)(static_cast<T*>(s_grad[d]) + (int64_t(n) * C + c0) * plane);
           T gix = T(0), giy = T(0);
-          if ((q.o_nw | q.o_ne | q.o_sw | q.o_se) >= 0) {
-            // interior tap (nearly all): 2 cc 8-byte texel loads, 4 cc window adds, the grid-gradient products
-            Pair<T> top[kChBlock], bot[kChBlock];
-#pragma unroll
-            for (int c = 0; c < kChBlock; ++c) {
-              top[c] = bot[c] = Pair<T>{T(0), T(0)};
-              if (c < cc && !DRTK_DBG(dbg, 2)) {
-                top[c] = *(GlobalPtr<const Pair<T>>)(inp + c * plane + q.o_nw);
-                bot[c] = *(GlobalPtr<const Pair<T>>)(inp + c * plane + q.o_sw);
-              }
-            }
-            int stride;
-            const int cell = cell_of(d, q.ix_nw, q.iy_nw, stride);
-            if (DRTK_DBG(dbg, 1)) {
-            } else if (cell >= 0) {
-              double* wp = win + cell;
-#pragma unroll
-              for (int c = 0; c < kChBlock; ++c) {
-                if (c >= cc) break;
-                lds_add(wp + c * kWaveCells, static_cast<double>(q.nw * g[c]));
-                lds_add(wp + c * kWaveCells + 1, static_cast<double>(q.ne * g[c]));
-                lds_add(wp + c * kWaveCells + stride, static_cast<double>(q.sw * g[c]));
-                lds_add(wp + c * kWaveCells + stride + 1, static_cast<double>(q.se * g[c]));
-              }
-            } else if (i < 16) {
-              pending |= 1u << (2 * i + s);
-              note_miss(s, q.ix_nw, q.iy_nw);
-            } else {
-              const GlobalPtr<T> gp = (GlobalPtr<T>)(static_cast<T*>(s_grad[d]) + (int64_t(n) * C + c0) * plane);
-#pragma unroll
-              for (int c = 0; c < kChBlock; ++c) {
-                if (c >= cc) break;
-                atomic_add_g1(gp + c * plane + q.o_nw, q.nw * g[c]);
-                atomic_add_g1(gp + c * plane + q.o_ne, q.ne * g[c]);
-                atomic_add_g1(gp + c * plane + q.o_sw, q.sw * g[c]);
-                atomic_add_g1(gp + c * plane + q.o_se, q.se * g[c]);
-              }
-            }
-            const T fy1 = iy_se - q.iy, fy0 = q.iy - q.iy_nw, fx1 = ix_se - q.ix, fx0 = q.ix - q.ix_nw;
-#pragma unroll
-            for (int c = 0; c < kChBlock; ++c) {
-              if (c >= cc) break;
-              const T gOut = g[c];
-              // with a zero upstream gradient every term is +-0 * finite: the texels count as 0
-              const T v_nw = gOut != T(0) ? top[c].x : T(0), v_ne = gOut != T(0) ? top[c].y : T(0);
-              const T v_sw = gOut != T(0) ? bot[c].x : T(0), v_se = gOut != T(0) ? bot[c].y : T(0);
-              gix -= v_nw * fy1 * gOut;
-              giy -= v_nw * fx1 * gOut;
-              gix += v_ne * fy1 * gOut;
-              giy -= v_ne * fx0 * gOut;
-              gix -= v_sw * fy0 * gOut;
-              giy += v_sw * fx1 * gOut;
-              gix += v_se * fy0 * gOut;
-              giy += v_se * fx0 * gOut;
-            }
-          } else {
-            // a tap on the border of its level: corner by corner, straight to global memory (the reference's form)
-            const GlobalPtr<T> gp = (GlobalPtr<T>)(static_cast<T*>(s_grad[d]) + (int64_t(n) * C + c0) * plane);
+          const int bx = cb.xi[0], by = cb.yi[0];
+          const bool interior = bx >= 0 && by >= 0 && cb.xi[1] == bx + 1 && cb.xi[2] == bx + 2 && cb.xi[3] == bx + 3 &&
+              cb.yi[1] == by + 1 && cb.yi[2] == by + 2 && cb.yi[3] == by + 3;
+          int stride = 0;
+          const int cell = interior ? cell_of(d, bx, by, stride) : -1;
+          const bool defer = interior && cell < 0 && i < 16 && !DRTK_DBG(dbg, 1);
+          if (defer) {
+            pending |= 1u << (2 * i + s);
+            note_miss(s, bx, by);
+          }
 #pragma unroll 1
-            for (int c = 0; c < cc; ++c) {
-              const T gOut = g[c];
-              if (gOut == T(0)) continue; // every term below would be +-0 * finite
-              const GlobalPtr<const T> p = inp + c * plane;
-              T v_nw = T(0), v_ne = T(0), v_sw = T(0), v_se = T(0);
-              if (!DRTK_DBG(dbg, 2)) {
-                if (q.o_nw >= 0) v_nw = p[q.o_nw];
-                if (q.o_ne >= 0) v_ne = p[q.o_ne];
-                if (q.o_sw >= 0) v_sw = p[q.o_sw];
-                if (q.o_se >= 0) v_se = p[q.o_se];
+          for (int c = 0; c < cc; ++c) {
+            const T gOut = go[c] * alpha;
+            if (gOut == T(0)) continue; // every term below would be +-0 * finite
+            const GlobalPtr<const T> pc = inp + c * plane;
+            if (DRTK_BICUBIC_ROWS && sizeof(T) == 4 && interior && !DRTK_DBG(dbg, 2)) { // (double: 12 registers spilled with the rows in flight)
+              // Round 6: the sixteen texels of an interior footprint as FOUR 16-byte row loads (element-aligned), like the
+              // forward -- they were sixteen predicated 4-byte loads, each in its own exec-mask region with its own wait
+              // (6.87 ms for RGB on the textured benchmark's inputs against 1.29 bilinear).  Same products, same order.
+              typedef T Quad4 __attribute__((ext_vector_type(4), aligned(sizeof(T))));
+              Quad4 row[4];
+#pragma unroll
+              for (int r = 0; r < 4; ++r) row[r] = *(GlobalPtr<const Quad4>)(pc + (by + r) * w + bx);
+              // ... and ROW BY ROW: the footprint's weights are an outer product xc (x) yc, so a row's four cells share
+              // gOut yc[j] and the grid gradient is  -gOut sum_j yc[j] (row_j . xg)  /  -gOut sum_j yg[j] (row_j . xc): 8
+              // multiply-adds per row instead of six operations per cell with their 48 hoisted coefficient products
+              // (the registers that held the kernel at two waves per SIMD)
+#pragma unroll
+              for (int j2 = 0; j2 < 4; ++j2) {
+                const T gy = gOut * yc[j2];
+                if (DRTK_DBG(dbg, 1)) {
+                } else if (cell >= 0) {
+                  double* wp = win + cell + c * kWaveCells + j2 * stride;
+#pragma unroll
+                  for (int i2 = 0; i2 < 4; ++i2) lds_add(wp + i2, static_cast<double>(gy * xc[i2]));
+                } else if (!defer) {
+                  const GlobalPtr<T> gq = gp + c * plane + ((by + j2) * w + bx);
+#pragma unroll
+                  for (int i2 = 0; i2 < 4; ++i2) atomic_add_g1(gq + i2, gy * xc[i2]);
+                }
+                const T sx = row[j2].x * xg[0] + row[j2].y * xg[1] + row[j2].z * xg[2] + row[j2].w * xg[3];
+                const T sc = row[j2].x * xc[0] + row[j2].y * xc[1] + row[j2].z * xc[2] + row[j2].w * xc[3];
+                gix -= gy * sx;
+                giy -= (gOut * yg[j2]) * sc;
               }
-              if (!DRTK_DBG(dbg, 1)) {
-                if (q.o_nw >= 0) atomic_add_g1(gp + c * plane + q.o_nw, q.nw * gOut);
-                if (q.o_ne >= 0) atomic_add_g1(gp + c * plane + q.o_ne, q.ne * gOut);
-                if (q.o_sw >= 0) atomic_add_g1(gp + c * plane + q.o_sw, q.sw * gOut);
-                if (q.o_se >= 0) atomic_add_g1(gp + c * plane + q.o_se, q.se * gOut);
+              continue;
+            }
+            if constexpr (DRTK_BICUBIC_COMPACT_SLOW && sizeof(T) == 4) {
+              // a footprint that touches the border of its level (rare): the sixteen cells in a loop that is NOT unrolled,
+              // coefficients and indices picked by selects -- the unrolled form below (sixteen predicated loads and their
+              // products in flight) is what kept this kernel at 225-243 registers = two waves per SIMD
+              auto sel4 = [](const auto (&a)[4], int k) { return k == 0 ? a[0] : k == 1 ? a[1] : k == 2 ? a[2] : a[3]; };
+#pragma unroll 1
+              for (int e = 0; e < 16; ++e) {
+                const int i2 = e >> 2, j2 = e & 3;
+                const int xi = sel4(cb.xi, i2), yi = sel4(cb.yi, j2);
+                const bool ok = xi >= 0 && yi >= 0;
+                const int o = ok ? yi * w + xi : 0;
+                const T cxw = sel4(xc, i2), cyw = sel4(yc, j2);
+                const T wgt = gOut * cxw * cyw;
+                if (DRTK_DBG(dbg, 1)) {
+                } else if (cell >= 0) { // (an interior footprint whose rows were not taken above: the ablation build only)
+                  lds_add(win + cell + c * kWaveCells + j2 * stride + i2, static_cast<double>(wgt));
+                } else if (ok && !defer) {
+                  atomic_add_g1(gp + c * plane + o, wgt);
+                }
+                const T val = (ok && !DRTK_DBG(dbg, 2)) ? pc[o] : T(0);
+                gix -= gOut * val * (sel4(xg, i2) * cyw);
+                giy -= gOut * val * (sel4(yg, j2) * cxw);
               }
-              if (q.o_nw >= 0) {
-                gix -= v_nw * (iy_se - q.iy) * gOut;
-                giy -= v_nw * (ix_se - q.ix) * gOut;
-              }
-              if (q.o_ne >= 0) {
-                gix += v_ne * (iy_se - q.iy) * gOut;
-                giy -= v_ne * (q.ix - q.ix_nw) * gOut;
-              }
-              if (q.o_sw >= 0) {
-                gix -= v_sw * (q.iy - q.iy_nw) * gOut;
-                giy += v_sw * (ix_se - q.ix) * gOut;
-              }
-              if (q.o_se >= 0) {
-                gix += v_se * (q.iy - q.iy_nw) * gOut;
-                giy += v_se * (q.ix - q.ix_nw) * gOut;
+              continue;
+            }
+#pragma unroll
+            for (int i2 = 0; i2 < 4; ++i2) {
+#pragma unroll
+              for (int j2 = 0; j2 < 4; ++j2) {
+                const bool ok = cb.xi[i2] >= 0 && cb.yi[j2] >= 0;
+                const int o = ok ? cb.yi[j2] * w + cb.xi[i2] : 0;
+                const T wgt = gOut * xc[i2] * yc[j2];
+                if (DRTK_DBG(dbg, 1)) {
+                } else if (cell >= 0) {
+                  lds_add(win + cell + c * kWaveCells + j2 * stride + i2, static_cast<double>(wgt));
+                } else if (ok && !defer) {
+                  atomic_add_g1(gp + c * plane + o, wgt);
+                }
+                const T val = (ok && !DRTK_DBG(dbg, 2)) ? pc[o] : T(0);
+                gix -= gOut * val * (xg[i2] * yc[j2]);
+                giy -= gOut * val * (yg[j2] * xc[i2]);
               }
             }
           }
-          acc_x += q.mx * gix;
-          acc_y += q.my * giy;
+          acc_x += cb.mx * gix;
+          acc_y += cb.my * giy;
         }
       }
     }
@@ -2713,63 +1990,34 @@ __global__ __launch_bounds__(kMipBlock, sizeof(T) == 8 ? 1 : (MODE == 2 ? DRTK_M
         const int h = s_h[d], w = s_w[d];
         const int plane = h * w;
         const T alpha = s2 == 0 ? alpha_2 : alpha_1;
-        if constexpr (MODE == 2) {
-          const Cubic<T> cb = bicubic_footprint<T>(x, y, h, w, padding, align_corners); // (interior: only those are deferred)
-          T xc[4], yc[4];
-          cubic_coeffs(xc, cb.tx);
-          cubic_coeffs(yc, cb.ty);
-          const int bx = cb.xi[0], by = cb.yi[0];
-          int stride;
-          const int cell = cell_of(d, bx, by, stride);
-          if (cell < 0 && !last) {
-            note_miss(s2, bx, by);
-            continue;
-          }
-          pending &= ~(1u << bit);
-          const GlobalPtr<T> gp = (GlobalPtr<T>)(static_cast<T*>(s_grad[d]) + (int64_t(n) * C + c0) * plane);
-#pragma unroll 1
-          for (int c = 0; c < cc; ++c) {
-            const T gOut = go[c] * alpha;
-            if (gOut == T(0)) continue;
-#pragma unroll
-            for (int i2 = 0; i2 < 4; ++i2) {
-#pragma unroll
-              for (int j2 = 0; j2 < 4; ++j2) {
-                const T wgt = gOut * xc[i2] * yc[j2];
-                if (cell >= 0) {
-                  lds_add(win + cell + c * kWaveCells + j2 * stride + i2, static_cast<double>(wgt));
-                } else {
-                  atomic_add_g1(gp + c * plane + (by + j2) * w + bx + i2, wgt);
-                }
-              }
-            }
-          }
-          continue;
-        }
-        const Quad<T> q = bilinear_quad<T>(x, y, h, w, padding, align_corners); // (interior: only those are deferred)
+        const Cubic<T> cb = bicubic_footprint<T>(x, y, h, w, padding, align_corners); // (interior: only those are deferred)
+        T xc[4], yc[4];
+        cubic_coeffs(xc, cb.tx);
+        cubic_coeffs(yc, cb.ty);
+        const int bx = cb.xi[0], by = cb.yi[0];
         int stride;
-        const int cell = cell_of(d, q.ix_nw, q.iy_nw, stride);
-        if (cell < 0 && !last) { // stays pending: the next round's window
-          note_miss(s2, q.ix_nw, q.iy_nw);
+        const int cell = cell_of(d, bx, by, stride);
+        if (cell < 0 && !last) {
+          note_miss(s2, bx, by);
           continue;
         }
         pending &= ~(1u << bit);
         const GlobalPtr<T> gp = (GlobalPtr<T>)(static_cast<T*>(s_grad[d]) + (int64_t(n) * C + c0) * plane);
+#pragma unroll 1
+        for (int c = 0; c < cc; ++c) {
+          const T gOut = go[c] * alpha;
+          if (gOut == T(0)) continue;
 #pragma unroll
-        for (int c = 0; c < kChBlock; ++c) {
-          if (c >= cc) break;
-          const T gc = go[c] * alpha;
-          if (cell >= 0) {
-            double* wp = win + cell + c * kWaveCells;
-            lds_add(wp, static_cast<double>(q.nw * gc));
-            lds_add(wp + 1, static_cast<double>(q.ne * gc));
-            lds_add(wp + stride, static_cast<double>(q.sw * gc));
-            lds_add(wp + stride + 1, static_cast<double>(q.se * gc));
-          } else {
-            atomic_add_g1(gp + c * plane + q.o_nw, q.nw * gc);
-            atomic_add_g1(gp + c * plane + q.o_ne, q.ne * gc);
-            atomic_add_g1(gp + c * plane + q.o_sw, q.sw * gc);
-            atomic_add_g1(gp + c * plane + q.o_se, q.se * gc);
+          for (int i2 = 0; i2 < 4; ++i2) {
+#pragma unroll
+            for (int j2 = 0; j2 < 4; ++j2) {
+              const T wgt = gOut * xc[i2] * yc[j2];
+              if (cell >= 0) {
+                lds_add(win + cell + c * kWaveCells + j2 * stride + i2, static_cast<double>(wgt));
+              } else {
+                atomic_add_g1(gp + c * plane + (by + j2) * w + bx + i2, wgt);
+              }
+            }
           }
         }
       }
@@ -2797,14 +2045,28 @@ int fill_table(
   return DRTK_OK;
 }
 
-// The lean kernels address a texel as `channel_in_block * plane + offset` in 32 bits (at most three planes + one): levels
-// beyond this size (a 23 170^2 level) take the general kernels, whose plane offsets are 64-bit.
-constexpr int64_t kLeanMaxPlane = ((int64_t(1) << 31) - 1) / 4;
-bool lean_planes_ok(const LevelTable& lv, int mipmaps) {
+// The lean kernels and the wave-private bicubic backward address a texel as `channel_in_block * plane + offset` in 32 bits
+// (at most three planes + one): a pyramid with a level beyond this size (a 23 171^2 level) takes the general kernels, whose
+// plane offsets are 64-bit.
+constexpr int64_t kMaxPlane32 = ((int64_t(1) << 31) - 1) / 4;
+bool planes_fit_32bit(const LevelTable& lv, int mipmaps) {
   for (int i = 0; i < mipmaps; ++i) {
-    if (int64_t(lv.h[i]) * lv.w[i] > kLeanMaxPlane) return false;
+    if (int64_t(lv.h[i]) * lv.w[i] > kMaxPlane32) return false;
   }
   return true;
+}
+
+// A run-time padding mode, align_corners or channel count as a compile-time constant: f(Int<V>{}) for the V of LO ... HI that
+// equals v (the entry points have checked the range; anything else takes HI).
+template <int V>
+using Int = std::integral_constant<int, V>;
+template <int LO, int HI, typename F>
+void with_constant(int v, F&& f) {
+  if constexpr (LO == HI) {
+    f(Int<LO>{});
+  } else {
+    if (v == LO) f(Int<LO>{}); else with_constant<LO + 1, HI>(v, f);
+  }
 }
 
 } // namespace
@@ -2830,40 +2092,38 @@ extern "C" int drtk_amd_mipmap_grid_sampler_2d(
   GridLayout gl;
   if (make_grid_layout(gl, grid_layout, grid, H, W, dtype == DRTK_F32 ? 4 : 8) != DRTK_OK) return DRTK_ERR_INVALID_ARGUMENT;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 grid_dim(static_cast<unsigned>(ceil_div(count, kBlock)));
-#define LAUNCH_P(T, MODE, PAD)                                                                                 \
-  DRTK_LAUNCH(                                                                                                 \
-      (mipmap_forward_kernel<T, MODE, PAD>), grid_dim, dim3(kBlock), 0, s, lv, mipmaps, static_cast<const T*>(grid), gl, \
-      static_cast<const T*>(vt_dxdy_img), count, (int)C, H * W, max_aniso, force_max_aniso != 0, clip_grad != 0, \
-      static_cast<T*>(out), xcd_strip(ceil_div(16 * W, kBlock)))
-#define LAUNCH(T, MODE)                                                                    \
-  if (padding_mode == 0) LAUNCH_P(T, MODE, 0); else if (padding_mode == 1) LAUNCH_P(T, MODE, 1); else LAUNCH_P(T, MODE, 2)
 #ifndef DRTK_MIP_FWD_LEAN
 #define DRTK_MIP_FWD_LEAN 1
 #endif
 #ifndef DRTK_MIP_FWD_LEAN_F64
 #define DRTK_MIP_FWD_LEAN_F64 1 // double takes the lean forward too (round 6)
 #endif
-#define LAUNCH_L(T, PAD, CB)                                                                                      \
-  DRTK_LAUNCH(                                                                                                 \
-      (mipmap_forward_lean_kernel<T, PAD, CB>), dim3(static_cast<unsigned>(ceil_div(H * W, kBlock)), static_cast<unsigned>(N)), \
-      dim3(kBlock), 0, s, lv, mipmaps, static_cast<const T*>(grid), gl, static_cast<const T*>(vt_dxdy_img), (int)C, \
-      H * W, max_aniso, force_max_aniso != 0, clip_grad != 0, static_cast<T*>(out), xcd_strip(ceil_div(16 * W, kBlock)))
-#define LAUNCH_LC(T, PAD)                                                                  \
-  if (C % 4 == 0) LAUNCH_L(T, PAD, 4); else if (C % 3 == 0) LAUNCH_L(T, PAD, 3); else if (C % 2 == 0) LAUNCH_L(T, PAD, 2); else LAUNCH_L(T, PAD, 1)
-  if (dtype == DRTK_F32 && interpolation_mode == 0 && N <= kMaxViewsPerLaunch && DRTK_MIP_FWD_LEAN && lean_planes_ok(lv, mipmaps)) {
-    if (padding_mode == 0) { LAUNCH_LC(float, 0); } else if (padding_mode == 1) { LAUNCH_LC(float, 1); } else { LAUNCH_LC(float, 2); }
-  } else if (dtype == DRTK_F64 && interpolation_mode == 0 && N <= kMaxViewsPerLaunch && DRTK_MIP_FWD_LEAN && DRTK_MIP_FWD_LEAN_F64 && lean_planes_ok(lv, mipmaps)) {
-    if (padding_mode == 0) { LAUNCH_LC(double, 0); } else if (padding_mode == 1) { LAUNCH_LC(double, 1); } else { LAUNCH_LC(double, 2); }
-  } else if (dtype == DRTK_F32) {
-    if (interpolation_mode == 0) { LAUNCH(float, 0); } else { LAUNCH(float, 2); }
-  } else {
-    if (interpolation_mode == 0) { LAUNCH(double, 0); } else { LAUNCH(double, 2); }
-  }
-#undef LAUNCH_LC
-#undef LAUNCH_L
-#undef LAUNCH
-#undef LAUNCH_P
+  auto launch = [&](auto tag) {
+    using T = decltype(tag);
+    const T* grid_t = static_cast<const T*>(grid);
+    const T* vt = static_cast<const T*>(vt_dxdy_img);
+    const int strip = xcd_strip(ceil_div(16 * W, kBlock));
+    with_constant<0, 2>(padding_mode, [&](auto pad) {
+      constexpr int PAD = decltype(pad)::value;
+      if (interpolation_mode == 0 && N <= kMaxViewsPerLaunch && DRTK_MIP_FWD_LEAN && (sizeof(T) == 4 || DRTK_MIP_FWD_LEAN_F64) &&
+          planes_fit_32bit(lv, mipmaps)) {
+        // bilinear: the lean kernel, as many channels per sweep over the taps as divide C
+        with_constant<1, 4>(C % 4 == 0 ? 4 : C % 3 == 0 ? 3 : C % 2 == 0 ? 2 : 1, [&](auto cb) {
+          DRTK_LAUNCH(
+              (mipmap_forward_lean_kernel<T, PAD, decltype(cb)::value>), dim3(static_cast<unsigned>(ceil_div(H * W, kBlock)), static_cast<unsigned>(N)),
+              dim3(kBlock), 0, s, lv, mipmaps, grid_t, gl, vt, (int)C, H * W, max_aniso, force_max_aniso != 0, clip_grad != 0,
+              static_cast<T*>(out), strip);
+        });
+      } else {
+        with_constant<0, 1>(interpolation_mode / 2, [&](auto bicubic) {
+          DRTK_LAUNCH(
+              (mipmap_forward_kernel<T, 2 * decltype(bicubic)::value, PAD>), dim3(static_cast<unsigned>(ceil_div(count, kBlock))), dim3(kBlock), 0, s,
+              lv, mipmaps, grid_t, gl, vt, count, (int)C, H * W, max_aniso, force_max_aniso != 0, clip_grad != 0, static_cast<T*>(out), strip);
+        });
+      }
+    });
+  };
+  if (dtype == DRTK_F32) launch(float{}); else launch(double{});
   DRTK_RETURN_IF_LAUNCH_FAILED();
   return DRTK_OK;
 }
@@ -2903,123 +2163,58 @@ extern "C" int drtk_amd_mipmap_grid_sampler_2d_backward(
   GridLayout gl, ggl;
   if (make_grid_layout(gl, grid_layout, grid, H, W, es) != DRTK_OK || make_grid_layout(ggl, grad_grid_layout, grad_grid, H, W, es) != DRTK_OK)
     return DRTK_ERR_INVALID_ARGUMENT;
-  // The windowed kernels (LDS accumulators in double whatever the element type) serve float and double alike: the
-  // reference dispatches both (kernel_utils.h:35-57).  Returns 1 when the shape is not theirs.
-  auto windowed = [&](auto tag) -> int {
+  // ONE rule.  A windowed kernel (LDS accumulators in double whatever the element type; float and double alike: the
+  // reference dispatches both, kernel_utils.h:35-57) runs only where a view is a grid row of the launch, there is a channel
+  // and every level fits the kernels' 32-bit `c * plane + offset`: bilinear takes the lean tile kernel, bicubic the
+  // wave-private one.  Everything else -- a larger level, more than kMaxViewsPerLaunch views, C = 0 (which only stores a zero
+  // grid gradient), ablation flag 512 -- takes the direct kernel, whose offsets are 64-bit and whose views are a division.
+  const bool windowed_ok = N <= kMaxViewsPerLaunch && C >= 1 && planes_fit_32bit(lv, mipmaps) && !DRTK_DBG(debug_flags(), 512);
+  auto launch = [&](auto tag) -> int {
     using T = decltype(tag);
-#ifndef DRTK_MIP_BWD_LEAN
-#define DRTK_MIP_BWD_LEAN 1
-#endif
-#ifndef DRTK_MIP_BWD_LEAN_F64
-#define DRTK_MIP_BWD_LEAN_F64 1 // double takes the lean tile kernel too (round 6; before: tiled2 at 240-256 registers)
-#endif
-#ifndef DRTK_MIP_BWD_LEAN_WIDE
-#define DRTK_MIP_BWD_LEAN_WIDE 1 // C > 4: the lean tile kernel once per block of four channels instead of the wave-private kernel
-#endif
-    if constexpr ((sizeof(T) == 4 || DRTK_MIP_BWD_LEAN_F64) && DRTK_MIP_BWD_LEAN) {
-      if (interpolation_mode == 0 && C >= 1 && N <= 65535 && !DRTK_DBG(debug_flags(), 512) &&
-          (C <= 4 || DRTK_MIP_BWD_LEAN_WIDE) && lean_planes_ok(lv, mipmaps)) { // bilinear, any padding, float and double: the lean tap loop, four channels a launch
-        const int tiles_x = static_cast<int>(ceil_div(W, kTileW)), tiles_y = static_cast<int>(ceil_div(H, kTileH));
-#define LEANK(PAD, ALIGN, CN)                                                                                           \
-  DRTK_LAUNCH(                                                                                                          \
-      (mipmap_backward_lean_kernel<T, PAD, ALIGN, CN>), dim3(static_cast<unsigned>(tiles_x * tiles_y), static_cast<unsigned>(N)), \
-      dim3(kMipBlock), sizeof(double) * CN * kWinLevels * lean_slot_cells<CN>(), s, lv, mipmaps, static_cast<const T*>(grad_out), \
-      static_cast<const T*>(grid), gl, static_cast<const T*>(vt_dxdy_img), (int)H, (int)W, tiles_x, max_aniso, \
-      force_max_aniso != 0, clip_grad != 0, static_cast<T*>(grad_grid), ggl, xcd_strip(tiles_x), debug_flags(), (int)C, c0)
-#define LEANC(PAD, ALIGN)                                                                       \
-  switch (cn) {                                                                                 \
-    case 1: LEANK(PAD, ALIGN, 1); break;                                                        \
-    case 2: LEANK(PAD, ALIGN, 2); break;                                                        \
-    case 3: LEANK(PAD, ALIGN, 3); break;                                                        \
-    default: LEANK(PAD, ALIGN, 4); break;                                                       \
-  }
-        for (int c0 = 0; c0 < C; c0 += 4) {
-          const int cn = static_cast<int>(C - c0 < 4 ? C - c0 : 4);
-          if (align_corners) {
-            if (padding_mode == 0) { LEANC(0, true) } else if (padding_mode == 1) { LEANC(1, true) } else { LEANC(2, true) }
-          } else {
-            if (padding_mode == 0) { LEANC(0, false) } else if (padding_mode == 1) { LEANC(1, false) } else { LEANC(2, false) }
-          }
-          DRTK_RETURN_IF_LAUNCH_FAILED();
+    const T* gout = static_cast<const T*>(grad_out);
+    const T* grid_t = static_cast<const T*>(grid);
+    const T* vt = static_cast<const T*>(vt_dxdy_img);
+    T* ggrid = static_cast<T*>(grad_grid);
+    if (!windowed_ok) {
+      with_constant<0, 1>(interpolation_mode / 2, [&](auto bicubic) {
+        DRTK_LAUNCH(
+            (mipmap_backward_kernel<T, 2 * decltype(bicubic)::value>), dim3(static_cast<unsigned>(ceil_div(count, kBlock))), dim3(kBlock), 0, s, lv,
+            mipmaps, gout, grid_t, gl, vt, count, (int)C, H * W, max_aniso, padding_mode, align_corners != 0, force_max_aniso != 0,
+            clip_grad != 0, ggrid, ggl, xcd_strip(ceil_div(16 * W, kBlock)));
+      });
+      DRTK_RETURN_IF_LAUNCH_FAILED();
+      return DRTK_OK;
+    }
+    const int tiles_x = static_cast<int>(ceil_div(W, kTileW)), tiles_y = static_cast<int>(ceil_div(H, kTileH));
+    const dim3 tiles(static_cast<unsigned>(tiles_x * tiles_y), static_cast<unsigned>(N));
+    int rc = DRTK_OK;
+    with_constant<0, 2>(padding_mode, [&](auto pad) {
+      with_constant<0, 1>(align_corners != 0, [&](auto align) {
+        constexpr int PAD = decltype(pad)::value;
+        constexpr bool ALIGN = decltype(align)::value != 0;
+        if (interpolation_mode == 2) {
+          // bicubic, any C: 4 x 4 cells per tap in wave-private windows, channels in blocks of four inside the kernel
+          const size_t lds = sizeof(double) * (C < kChBlock ? C : kChBlock) * kWaveCells * (kMipBlock / kWave);
+          DRTK_LAUNCH(
+              (mipmap_backward_wave_kernel<T, PAD, ALIGN>), tiles, dim3(kMipBlock), lds, s, lv, mipmaps, gout, grid_t, gl, vt, (int)H,
+              (int)W, (int)C, tiles_x, max_aniso, force_max_aniso != 0, clip_grad != 0, ggrid, ggl, xcd_strip(tiles_x), debug_flags());
+          if (hipGetLastError() != hipSuccess) rc = DRTK_ERR_LAUNCH;
+          return;
         }
-#undef LEANC
-#undef LEANK
-        return DRTK_OK;
-      }
-    }
-  // bilinear: C <= 4 takes the workgroup-tiled kernel, wider textures (neural textures, 8-16 channels) the
-  // wave-private one in blocks of four channels -- before round 4 they fell to the direct kernel, bound by the float-atomic
-  // request rate.  (-DDRTK_MIP_BACKWARD_WAVE_ALL: the wave kernel for every C, for A/B; at C = 3 it is slower than the
-  // tiled one -- 2.52 against 1.95 ms on the textured benchmark at the same 3 waves per SIMD.)
-#ifdef DRTK_MIP_BACKWARD_WAVE_ALL
-  constexpr int64_t kWaveFromC = 1;
-#else
-  constexpr int64_t kWaveFromC = 5;
-#endif
-  // bicubic (any C >= 1): the same wave-private windows with 4 x 4 cells per tap (before round 4: the direct kernel,
-  // sixteen global float atomics per tap, level and channel -- 89 ms against 1.96 ms bilinear on the textured benchmark)
-  if (((interpolation_mode == 0 && C >= kWaveFromC) || (interpolation_mode == 2 && C >= 1)) && N <= 65535 &&
-      !DRTK_DBG(debug_flags(), 512)) {
-    const int tiles_x = static_cast<int>(ceil_div(W, kTileW)), tiles_y = static_cast<int>(ceil_div(H, kTileH));
-    const size_t lds = sizeof(double) * (C < kChBlock ? C : kChBlock) * kWaveCells * (kMipBlock / kWave);
-#define WAVEK(PAD, ALIGN)                                                                                               \
-  if (interpolation_mode == 2)                                                                                          \
-    DRTK_LAUNCH(                                                                                                        \
-        (mipmap_backward_wave_kernel<T, PAD, ALIGN, 2>), dim3(static_cast<unsigned>(tiles_x * tiles_y), static_cast<unsigned>(N)), \
-        dim3(kMipBlock), lds, s, lv, mipmaps, static_cast<const T*>(grad_out), static_cast<const T*>(grid), gl, \
-        static_cast<const T*>(vt_dxdy_img), (int)H, (int)W, (int)C, tiles_x, max_aniso, force_max_aniso != 0,     \
-        clip_grad != 0, static_cast<T*>(grad_grid), ggl, xcd_strip(tiles_x), debug_flags());                        \
-  else                                                                                                                  \
-  DRTK_LAUNCH(                                                                                                          \
-      (mipmap_backward_wave_kernel<T, PAD, ALIGN>), dim3(static_cast<unsigned>(tiles_x * tiles_y), static_cast<unsigned>(N)), \
-      dim3(kMipBlock), lds, s, lv, mipmaps, static_cast<const T*>(grad_out), static_cast<const T*>(grid), gl,  \
-      static_cast<const T*>(vt_dxdy_img), (int)H, (int)W, (int)C, tiles_x, max_aniso, force_max_aniso != 0,        \
-      clip_grad != 0, static_cast<T*>(grad_grid), ggl, xcd_strip(tiles_x), debug_flags())
-    if (align_corners) {
-      if (padding_mode == 0) WAVEK(0, true); else if (padding_mode == 1) WAVEK(1, true); else WAVEK(2, true);
-    } else {
-      if (padding_mode == 0) WAVEK(0, false); else if (padding_mode == 1) WAVEK(1, false); else WAVEK(2, false);
-    }
-#undef WAVEK
-    DRTK_RETURN_IF_LAUNCH_FAILED();
-    return DRTK_OK;
-  }
-  if (interpolation_mode == 0 && C <= 4 && N <= 65535 && !DRTK_DBG(debug_flags(), 512)) {
-    const int tiles_x = static_cast<int>(ceil_div(W, kTileW)), tiles_y = static_cast<int>(ceil_div(H, kTileH));
-#define TILED(PAD, ALIGN)                                                                                                \
-  DRTK_LAUNCH(                                                                                                           \
-      (mipmap_backward_tiled2_kernel<T, PAD, ALIGN>), dim3(static_cast<unsigned>(tiles_x * tiles_y), static_cast<unsigned>(N)), \
-      dim3(kMipBlock), sizeof(double) * C * kWinCells, s, lv, mipmaps, static_cast<const T*>(grad_out),              \
-      static_cast<const T*>(grid), gl, static_cast<const T*>(vt_dxdy_img), (int)H, (int)W, (int)C, tiles_x, max_aniso, \
-      force_max_aniso != 0, clip_grad != 0, static_cast<T*>(grad_grid), ggl, xcd_strip(tiles_x), debug_flags())
-    if (align_corners) {
-      if (padding_mode == 0) TILED(0, true); else if (padding_mode == 1) TILED(1, true); else TILED(2, true);
-    } else {
-      if (padding_mode == 0) TILED(0, false); else if (padding_mode == 1) TILED(1, false); else TILED(2, false);
-    }
-#undef TILED
-    DRTK_RETURN_IF_LAUNCH_FAILED();
-    return DRTK_OK;
-  }
-    return 1;
+        // bilinear: the lean tile kernel, once per block of four channels (every launch after the first adds to the grid gradient)
+        for (int c0 = 0; c0 < C && rc == DRTK_OK; c0 += 4) {
+          with_constant<1, 4>(static_cast<int>(C - c0 < 4 ? C - c0 : 4), [&](auto cn) {
+            constexpr int CN = decltype(cn)::value;
+            DRTK_LAUNCH(
+                (mipmap_backward_lean_kernel<T, PAD, ALIGN, CN>), tiles, dim3(kMipBlock), sizeof(double) * CN * kWinLevels * lean_slot_cells<CN>(),
+                s, lv, mipmaps, gout, grid_t, gl, vt, (int)H, (int)W, tiles_x, max_aniso, force_max_aniso != 0, clip_grad != 0, ggrid, ggl,
+                xcd_strip(tiles_x), debug_flags(), (int)C, c0);
+          });
+          if (hipGetLastError() != hipSuccess) rc = DRTK_ERR_LAUNCH;
+        }
+      });
+    });
+    return rc;
   };
-  {
-    const int w = dtype == DRTK_F32 ? windowed(float{}) : windowed(double{});
-    if (w != 1) return w;
-  }
-  const dim3 grid_dim(static_cast<unsigned>(ceil_div(count, kBlock)));
-#define LAUNCH(T, MODE)                                                                                       \
-  DRTK_LAUNCH(                                                                                         \
-      (mipmap_backward_kernel<T, MODE>), grid_dim, dim3(kBlock), 0, s, lv, mipmaps, static_cast<const T*>(grad_out), \
-      static_cast<const T*>(grid), gl, static_cast<const T*>(vt_dxdy_img), count, (int)C, H * W, max_aniso, padding_mode, \
-      align_corners != 0, force_max_aniso != 0, clip_grad != 0, static_cast<T*>(grad_grid), ggl,                  \
-      xcd_strip(ceil_div(16 * W, kBlock)))
-  if (dtype == DRTK_F32) {
-    if (interpolation_mode == 0) LAUNCH(float, 0); else LAUNCH(float, 2);
-  } else {
-    if (interpolation_mode == 0) LAUNCH(double, 0); else LAUNCH(double, 2);
-  }
-#undef LAUNCH
-  DRTK_RETURN_IF_LAUNCH_FAILED();
-  return DRTK_OK;
+  return dtype == DRTK_F32 ? launch(float{}) : launch(double{});
 }

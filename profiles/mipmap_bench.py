@@ -17,7 +17,7 @@ ap.add_argument("--res", type=int, default=4096)
 ap.add_argument("--views", type=int, default=2)
 ap.add_argument("--tex", type=int, default=4096)
 ap.add_argument("--reps", type=int, default=5)
-ap.add_argument("--channels", type=int, default=3, help="texture channels (3 = the textured configuration; 8 / 16: neural textures -- the wave-private backward kernel)")
+ap.add_argument("--channels", type=int, default=3, help="texture channels (3 = the textured configuration; 8 / 16: neural textures -- the lean backward once per block of four channels)")
 ap.add_argument("--bicubic", action="store_true")
 ap.add_argument("--padding", default="border", choices=["zeros", "border", "reflection"], help="padding mode (the textured configuration samples with border)")
 ap.add_argument("--uv", action="store_true", help="also time screen_space_uv_derivative on the same scene (through the C ABI: --lib applies)")

@@ -855,3 +855,134 @@ def test_kernel_gives_the_hand_derived_known_answers():
         K.run_B(via_capi, dt)
     K.run_A(via_python_api)
     K.run_B(via_python_api)
+
+
+def backward_and_its_kernels(*args):
+    """capi.mipmap_grid_sampler_2d_backward(*args) and the names of the sampler's backward kernels it launched."""
+    from drtk_amd import capi
+
+    capi.kernel_timing_begin()
+    got = capi.mipmap_grid_sampler_2d_backward(*args)
+    th.cuda.synchronize()
+    names = {k.strip("()").split("<")[0] for k in capi.kernel_timing_report()}
+    return got, {k for k in names if k.startswith("mipmap_backward")}
+
+
+@pytest.mark.parametrize("dtype", [th.float32, th.float64])
+@pytest.mark.parametrize("mode,C,kernel", [(0, C, "mipmap_backward_lean_kernel") for C in (1, 3, 4, 5, 8)] +
+                         [(2, C, "mipmap_backward_wave_kernel") for C in (1, 5)] +
+                         [(mode, 0, "mipmap_backward_kernel") for mode in (0, 2)])
+def test_which_backward_kernel_a_call_takes(mode, C, kernel, dtype):
+    """The routing table of drtk_amd_mipmap_grid_sampler_2d_backward: where every level fits the windowed kernels' 32-bit
+    texel offsets, bilinear takes the lean tile kernel (once per block of four channels) and bicubic the wave-private one, in
+    float and double; a call without channels takes the direct kernel, which only stores the zero grid gradient."""
+    if C == 0:
+        _, grid, vt, _ = mipmap_inputs(6200 + mode, 2, 1, 16, 3, 8, 8, dtype)
+        tex, gout = [th.zeros(2, 0, 16 >> l, 16 >> l, dtype=dtype) for l in range(3)], th.zeros(2, 0, 8, 8, dtype=dtype)
+    else:
+        tex, grid, vt, gout = mipmap_inputs(6200 + 10 * C + mode, 2, C, 16, 3, 8, 8, dtype)
+    (glv, gg), launched = backward_and_its_kernels(dev(gout), dev(tex), dev(grid), dev(vt), 4, 1, mode)
+    assert launched == {kernel}
+    if C == 0:
+        assert float(gg.abs().max()) == 0.0 and all(g.numel() == 0 for g in glv)
+
+
+@pytest.mark.parametrize("mode", [0, 2])
+def test_more_views_than_one_launch_take_the_direct_kernels(mode):
+    """65 536 + 3 views -- more than the grid rows of a launch, which is what a view is to the lean and windowed kernels: the
+    general forward and the direct backward (one thread per pixel, the view by division), against the oracle."""
+    import oracle as O
+    from drtk_amd import capi
+
+    N = 65536 + 3
+    tex, grid, vt, gout = mipmap_inputs(6300 + mode, N, 1, 4, 3, 2, 2)
+    want = O.mipmap_grid_sampler_2d(tex, grid, vt, 4, 1, mode, False, False, False)
+    close(capi.mipmap_grid_sampler_2d(dev(tex), dev(grid), dev(vt), 4, 1, mode, False, False, False), want, "forward")
+    wl, wg = O.mipmap_grid_sampler_2d_backward(gout, tex, grid, vt, 4, 1, mode, False, False, False)
+    (gl, gg), launched = backward_and_its_kernels(dev(gout), dev(tex), dev(grid), dev(vt), 4, 1, mode, False, False, False)
+    assert launched == {"mipmap_backward_kernel"}
+    close(gg, wg, "grad grid", atol=2e-5)
+    for i, (a, b) in enumerate(zip(gl, wl)):
+        close(a, b, f"grad level {i}")
+
+
+BIG_H, BIG_W = 8192, 70000  # one level of 573 440 000 texels: more than (2^31 - 1) / 4
+
+
+@pytest.fixture(scope="module")
+def big_level():
+    """A single level [1, 4, 8192, 70000] on the device (9.2 GB; channel 0 on the host as well) and a 4 x 8 pixel image that
+    looks at its four corners, its interior and -- 20 of the 32 pixels -- its last 500 rows: a texel's byte offset passes 2^31
+    from row 7 670 on, and `3 * plane + offset` passes 2^31 texels from row 6 101 on.  Footprints of about one texel per pixel
+    and up to four taps."""
+    if th.cuda.get_device_properties(0).total_memory < 64 * 2**30:
+        pytest.skip("needs ~25 GB of device memory")
+    g = th.Generator(device=DEV).manual_seed(9)
+    tex4 = th.rand(1, 4, BIG_H, BIG_W, device=DEV, generator=g)
+    xy = [(-0.5, -0.5), (BIG_W - 0.5, -0.5), (-0.5, BIG_H - 0.5), (BIG_W - 0.5, BIG_H - 0.5),
+          (35000.3, 4000.6), (123.25, 77.5), (69990.7, 100.2), (5.5, 6000.4), (60000.1, 6101.3), (1000.9, 6500.5), (42000.4, 7000.2),
+          (69998.6, 7669.7)]
+    xy += [((k * 3683.7 + 11.4) % (BIG_W - 1), 7692.31 + k * 26.2) for k in range(18)] + [(69999.2, 8190.8), (0.3, 8190.4)]
+    xy = th.tensor(xy, dtype=th.float64)
+    assert xy.shape == (32, 2) and int((xy[:, 1] >= BIG_H - 500).sum()) >= 20
+    uv = th.stack([(2 * xy[:, 0] + 1) / BIG_W - 1, (2 * xy[:, 1] + 1) / BIG_H - 1], -1)
+    uv[:4] = th.tensor([[-1.0, -1.0], [1.0, -1.0], [-1.0, 1.0], [1.0, 1.0]], dtype=th.float64)
+    grid = uv.float().view(1, 4, 8, 2)
+    k = th.arange(32)
+    jac = th.zeros(32, 2, 2, dtype=th.float64)
+    jac[:, 0, 0] = th.tensor([1.0, 2.5, 4.0, 0.6])[k % 4] * 2 / BIG_W   # du/dx: 0.6 to 4 texels
+    jac[:, 0, 1] = 0.1 * 2 / BIG_H
+    jac[:, 1, 0] = 0.1 * 2 / BIG_W
+    jac[:, 1, 1] = th.tensor([1.0, 0.8, 1.7])[k % 3] * 2 / BIG_H        # dv/dy
+    gout = th.rand(1, 4, 4, 8, generator=th.Generator().manual_seed(10)) * 2 - 1
+    yield dict(tex4=tex4, tex_host=tex4[:, :1].cpu(), grid=grid, vt=jac.float().view(1, 4, 8, 2, 2), gout=gout)
+    del tex4
+    th.cuda.empty_cache()
+
+
+def close_on_device(a, ref, what, atol=1e-5, rtol=1e-5):
+    """close() for tensors that stay on the device (float32 differences: the tensors are gigabytes)."""
+    assert a.shape == ref.shape, (what, a.shape, ref.shape)
+    tol = atol + rtol * float(ref.abs().max())
+    err = float(th.sub(a, ref).abs_().max())
+    assert err <= tol, f"{what}: max abs err {err:.3e} > tol {tol:.3e}"
+
+
+@pytest.mark.parametrize("mode", [0, 2])
+def test_a_level_beyond_the_32_bit_bound_takes_the_direct_kernel(big_level, mode):
+    """A level of more than (2^31 - 1) / 4 texels does not fit the windowed kernels' 32-bit `c * plane + offset`: bilinear and
+    bicubic calls take the direct kernel, whose offsets are 64-bit.  (a) one channel: forward and both gradients against the
+    oracle -- the level gradient where either side is non-zero, and the same number of non-zeros; (b) four channels (the
+    fourth channel's offsets pass 2^31 texels): every channel's level gradient equals the one-channel call on that channel's
+    slice and the grid gradient the sum of the four, on the device.  Wall time on an MI355X: see profiles/NOTES.md R9."""
+    import oracle as O
+    from drtk_amd import capi
+
+    s = big_level
+    grid, vt, gout = s["grid"], s["vt"], s["gout"]
+    dgrid, dvt, dgout = dev(grid), dev(vt), dev(gout)
+    args = (4, 1, mode, False, False, False)
+    # (a)
+    host, tex1 = [s["tex_host"]], [s["tex4"][:, :1]]
+    close(capi.mipmap_grid_sampler_2d(tex1, dgrid, dvt, *args), O.mipmap_grid_sampler_2d(host, grid, vt, *args), "forward")
+    wl, wg = O.mipmap_grid_sampler_2d_backward(gout[:, :1], host, grid, vt, *args)
+    (gl, gg), launched = backward_and_its_kernels(dgout[:, :1].contiguous(), tex1, dgrid, dvt, *args)
+    assert launched == {"mipmap_backward_kernel"}
+    close(gg, wg, "grad grid", atol=2e-5)
+    nz_got, nz_want = th.nonzero(gl[0].view(-1)).view(-1).cpu(), th.nonzero(wl[0].view(-1)).view(-1)
+    either = th.unique(th.cat([nz_got, nz_want]))
+    assert int(either.max()) * 4 >= 2**31 and int(either.min()) == 0, "scene: texels on both sides of the 2^31-byte offset are written"
+    close(gl[0].view(-1)[either.to(DEV)], wl[0].view(-1)[either], "grad level, where either side is non-zero")
+    assert nz_got.numel() == nz_want.numel(), f"non-zero texel gradients: {nz_got.numel()} against the oracle's {nz_want.numel()}"
+    del gl, wl
+    # (b)
+    (gl4, gg4), launched = backward_and_its_kernels(dgout, [s["tex4"]], dgrid, dvt, *args)
+    assert launched == {"mipmap_backward_kernel"}
+    gg_sum = th.zeros_like(gg4)
+    for c in range(4):
+        (gl1, gg1), _ = backward_and_its_kernels(dgout[:, c:c + 1].contiguous(), [s["tex4"][:, c:c + 1]], dgrid, dvt, *args)
+        assert int(th.count_nonzero(gl1[0])) > 0
+        close_on_device(gl4[0][:, c:c + 1], gl1[0], f"grad level, channel {c} of four against the one-channel call")
+        gg_sum += gg1
+        del gl1
+    close(gg4, gg_sum.cpu(), "grad grid of four channels against the sum of the one-channel calls", atol=2e-5)
