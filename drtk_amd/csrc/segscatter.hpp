@@ -19,7 +19,10 @@
 //     one per run.  The table is private to the wave, so the wide (C = 16) path updates it with
 //     plain read-modify-write (measured: LDS float atomics retire ~1 lane per clock and were the
 //     bottleneck of a workgroup-shared table).  Vertices that do not fit (table full) fall back to
-//     a direct global atomic, so any input is handled.
+//     a direct global atomic, so any input is handled.  (Held by tests/test_gpu_scatter_tables.py:
+//     index images built so that the table MUST overflow, that a probe sequence runs out in a nearly
+//     empty table, and that one vertex goes both ways in one launch -- rasterized images are too
+//     coherent to get there.)
 #pragma once
 
 #include <type_traits>

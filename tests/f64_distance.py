@@ -51,6 +51,16 @@ def assert_within_f64_distance(got_f32, oracle_f32, oracle_f64, what, k=3.0, rel
     return err, own
 
 
+
+def assert_normal_matrix_values_within(got_f32, oracle_f32, oracle_f64, what):
+    """The float32 bound of the A^T A values (interpolation_normal_matrix_values): an entry sums one product per pixel of the
+    triangles around a vertex pair, and every term is a product of non-negative barycentrics, so the magnitude accumulated
+    into an entry is the entry itself -- the largest of them is the accumulation term of the max-norm bound above.  One
+    statement for tests/fuzz_next_ops.py and tests/test_gpu_scatter_tables.py."""
+    acc = float(oracle_f64.abs().max()) if oracle_f64.numel() else 0.0
+    return assert_within_f64_distance(got_f32, oracle_f32, oracle_f64, what, acc_magnitude=acc)
+
+
 # ---- per element (round 6) -------------------------------------------------------------------------------------------------
 # The bound above is a MAX-NORM bound: with max|ref| ~ 40 it lets a vertex whose whole gradient is 1e-4 be 100 % wrong.
 # What a float32 sum can be held to per element is the magnitude that was accumulated INTO THAT ELEMENT,

@@ -16,7 +16,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 
 DEV = "cuda:0"
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from f64_distance import assert_within_f64_distance  # noqa: E402
+from f64_distance import assert_normal_matrix_values_within  # noqa: E402
 
 # screen_space_uv_derivative: quantiles of the per-pixel error against the double result, the kernel's within this factor
 # of the reference composite's own (the same principle as tests/f64_distance.py, on a distribution instead of a maximum).
@@ -126,9 +126,8 @@ def _run_case(c):
         # (tests/f64_distance.py); every term is a product of non-negative barycentrics, so what was accumulated is the
         # entry itself.
         nv_64 = O.normal_matrix_values(pair_o, index, bary.double(), nnz)
-        acc = float(nv_64.abs().max()) if nv_64.numel() else 0.0
-        assert_within_f64_distance(M.values(), nv_o, nv_64, "A^T A values (python api)", acc_magnitude=acc)
-        assert_within_f64_distance(capi.interpolation_normal_matrix_values(d(pair_o), dindex, dbary, nnz), nv_o, nv_64, "A^T A values", acc_magnitude=acc)
+        assert_normal_matrix_values_within(M.values(), nv_o, nv_64, "A^T A values (python api)")
+        assert_normal_matrix_values_within(capi.interpolation_normal_matrix_values(d(pair_o), dindex, dbary, nnz), nv_o, nv_64, "A^T A values")
     tol = dict(atol=1e-12, rtol=1e-10) if f64 else dict(atol=1e-5, rtol=1e-5)
     gnm = (th.rand(nnz, generator=g, dtype=th.float64) * 2 - 1).to(dtype)
     _close(capi.interpolation_normal_matrix_values_backward(d(gnm), d(pair_o), dindex, dbary), O.normal_matrix_values_backward(gnm, pair_o, index, bary),
