@@ -47,6 +47,25 @@ struct Vec4<double> {
 template <typename T>
 using Quad = T __attribute__((ext_vector_type(4), aligned(sizeof(T))));
 
+// The batched loads of the one-pass kernel (edge_dots_kernel, SCATTER) go through raw buffer descriptors: a wave-uniform
+// base with the exact byte size of what it covers -- one view's plane, one view's corner or vertex table -- and a 32-bit
+// byte offset per lane.  The hardware checks every dword of an access against that size: what lies beyond it is not
+// fetched and reads as 0, so a lane that has nothing to load is given the size itself as its offset instead of a branch
+// around the load, and a batch of such loads is issued back to back under one wait.  (A load under a lane condition is
+// compiled as a branch with its own s_waitcnt vmcnt(0): one round trip per load.)
+using BufferRsrc = __amdgpu_buffer_rsrc_t;
+__device__ __forceinline__ BufferRsrc buffer_rsrc(const void* base, uint32_t bytes) { // both wave-uniform
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, static_cast<int>(bytes), 0x00020000);
+}
+// (a loaded vector's element passes through this argument: __builtin_bit_cast applied to the element expression itself
+// reads element 0 whichever is named)
+__device__ __forceinline__ float as_float(uint32_t bits) {
+  return __builtin_bit_cast(float, bits);
+}
+__device__ __forceinline__ int32_t buffer_load_i32(BufferRsrc r, uint32_t byte_offset) {
+  return static_cast<int32_t>(__builtin_amdgcn_raw_buffer_load_b32(r, byte_offset, 0, 0));
+}
+
 // ---------------------------------------------------------------------------------------------
 // Pass A
 // ---------------------------------------------------------------------------------------------
@@ -106,9 +125,15 @@ struct PairArgs {
   const int32_t* vi;
   const T* bary_img;
   T* grad_v_pix;
-  int64_t V, vi_sN;
+  int64_t V, vi_sN, F;
   T M;
 };
+
+// Rounds of 64 pairs that the classification phase of the one-pass kernel keeps in flight (needed_pair_flags).  Three fit
+// the 80 registers as well; four spill 17 of them (the build refuses spills).  Measured: profiles/NOTES.md R10.
+#ifndef DRTK_EDGE_CLASSIFY_ROUNDS
+#define DRTK_EDGE_CLASSIFY_ROUNDS 2
+#endif
 
 // exclusive prefix over the lanes of a 0..4 count, and its wave total, from three ballots (lt = the lanes below this one)
 __device__ __forceinline__ int prefix4(int cnt, unsigned long long lt, int& total) {
@@ -123,10 +148,10 @@ __device__ __forceinline__ void scatter_pair_round(
     const int32_t* __restrict__ vi_n, const T* __restrict__ bary_n, int64_t HW, int W, T M, int32_t* keys,
     TableAcc* vals, T* __restrict__ grad_n);
 
-template <typename T, int R>
+template <typename T, int R, int P>
 __device__ __forceinline__ uint32_t needed_pair_flags(
-    uint32_t flags, int lane, int strip_x0, int y0, const int32_t* __restrict__ idx_n, const T* __restrict__ v_n,
-    const int32_t* __restrict__ vi_n, int W, uint32_t* list, uint32_t* mask);
+    uint32_t flags, int lane, int strip_x0, int y0, BufferRsrc idx_rsrc, uint32_t idx_bytes, BufferRsrc v_rsrc,
+    uint32_t v_bytes, BufferRsrc vi_rsrc, uint32_t vi_bytes, int W, uint32_t* list, uint32_t* mask);
 
 // One wave = strip of 63*VEC pixels (+ VEC halo pixels in lane 63) x R rows; the WAVES waves of a workgroup are stacked vertically
 // on the same pixel columns (WAVES*R rows per workgroup), so the extra "row below" every wave needs
@@ -152,6 +177,11 @@ __device__ __forceinline__ uint32_t needed_pair_flags(
 // overlap or an intersection: silhouettes and self-occlusion contours.  What a lane loads follows those flags: a lane
 // without a needed pair (and whose first pixel its left neighbour does not need) loads nothing, a wave without one returns
 // before the channel loop (four strips in five on the bench scene), and the pair phase sees the needed pairs only.
+// Such a wave is a chain of dependent loads, not a stream, so in this mode every phase issues its loads TOGETHER and
+// waits once (BufferRsrc above: range-checked loads instead of branches): the R + 1 index rows, then per P rounds of the
+// classification all ids, all faces, all vertices, then per channel the 2 (R + 1) image rows; the shuffles that hand a
+// lane's first pixel to its left neighbour come after the loads of their phase.  (Written with a load under each lane
+// condition: six round trips for the index rows, three per round of 64 pairs, five to six per channel.)
 template <typename T, int VEC, int R, int WAVES, bool SCATTER = false>
 __global__ __launch_bounds__(WAVES * kWave, SCATTER ? DRTK_ONEPASS_WAVES : 1) void edge_dots_kernel(
     const T* __restrict__ img, const T* __restrict__ grad_output, const int32_t* __restrict__ index_img, int C,
@@ -194,16 +224,54 @@ __global__ __launch_bounds__(WAVES * kWave, SCATTER ? DRTK_ONEPASS_WAVES : 1) vo
   bool any_fg = false;
   // SCATTER: the pairs this lane owns whose indices differ -- bit 4r+j: (x+j,y0+r)-(x+j+1,y0+r), bit 4R+4r+j: (x+j,y0+r)-(x+j,y0+r+1)
   uint32_t flags = 0;
-  {
+  // SCATTER: what the batched loads of a plane of this view take -- the plane's size in bytes (H W <= 2^30 - 8 on this path,
+  // checked by the launcher) and, per row of the strip, the byte offset of this lane's four pixels in the plane; a lane
+  // off the canvas and a row below the image get the plane's size: beyond the descriptor, nothing is fetched
+  const uint32_t plane_bytes = static_cast<uint32_t>(HW) * 4u;
+  uint32_t row_off[R + 1];
+#pragma unroll
+  for (int r = 0; r <= R; ++r) row_off[r] = (x < W && y0 + r < H) ? static_cast<uint32_t>((y0 + r) * W + x) * 4u : plane_bytes;
+  const BufferRsrc idx_rsrc = buffer_rsrc(index_img + int64_t(n) * HW, plane_bytes);
+  if constexpr (SCATTER) {
+    // The quads of all R + 1 index rows in ONE round trip, the shuffles after them.  Each load stays inside this view's
+    // index plane: the descriptor covers exactly its H W elements, and an element of a quad that lies beyond the end of
+    // its row (the next row's first pixels, or nothing) is replaced by -1 after the load.  Neither lane 0's left
+    // neighbour nor lane 63's right one is loaded: lane 63 owns no pair, and no pair looks to the left.
+    int32_t cur[R + 1][4];
+#pragma unroll
+    for (int r = 0; r <= R; ++r) {
+      const auto q = __builtin_amdgcn_raw_buffer_load_b128(idx_rsrc, row_off[r], 0, 0);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) cur[r][j] = static_cast<int32_t>(q[j]);
+    }
+#pragma unroll
+    for (int r = 0; r <= R; ++r)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) cur[r][j] = (x + j < W && y0 + r < H) ? cur[r][j] : -1;
+    int32_t right[R + 1]; // the next lane's first pixel (the halo row has no horizontal pair)
+#pragma unroll
+    for (int r = 0; r < R; ++r) right[r] = __shfl_down(cur[r][0], 1);
+    right[R] = -1;
+#pragma unroll
+    for (int r = 0; r <= R; ++r) {
+      const int y = y0 + r;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const bool in_x = lane != kWave - 1 && x + j < W - 1; // stencil domain of the reference; lane 63 owns nothing
+        // vertical pairs of the row before, if this row exists (then y - 1 < H - 1)
+        if (r > 0 && y < H && in_x && cur[r > 0 ? r - 1 : 0][j] != cur[r][j]) flags |= 1u << (4 * R + 4 * (r - 1) + j);
+        const int32_t nr = j < 3 ? cur[r][(j + 1) & 3] : right[r];
+        if (r < R && in_x && y < H - 1 && cur[r][j] != nr) flags |= 1u << (4 * r + j);
+      }
+    }
+  } else {
     const int32_t* idx_n = index_img + int64_t(n) * HW;
-    int32_t above[4] = {-1, -1, -1, -1}; // SCATTER: the row before this one
 #pragma unroll
     for (int r = 0; r <= R; ++r) {
       const int y = y0 + r;
       if (y < H) { // wave-uniform
         bool fg = false;
         int32_t first = -1, last = -1;
-        int32_t cur[4] = {-1, -1, -1, -1};
         if (x < W) {
           if constexpr (VEC == 4) {
             Quad<int32_t> q;
@@ -215,7 +283,6 @@ __global__ __launch_bounds__(WAVES * kWave, SCATTER ? DRTK_ONEPASS_WAVES : 1) vo
             }
             fg = (q.x & q.y & q.z & q.w) != -1;
             first = q.x, last = q.w;
-            cur[0] = q.x, cur[1] = q.y, cur[2] = q.z, cur[3] = q.w;
           } else {
             first = last = idx_n[int64_t(y) * W + x];
             fg = first != -1;
@@ -225,17 +292,6 @@ __global__ __launch_bounds__(WAVES * kWave, SCATTER ? DRTK_ONEPASS_WAVES : 1) vo
         if (lane == 0) left = (x >= 1 && x < W) ? idx_n[int64_t(y) * W + x - 1] : -1;
         if (lane == kWave - 1) right = (x + VEC < W) ? idx_n[int64_t(y) * W + x + VEC] : -1;
         any_fg = any_fg || fg || left != -1 || right != -1;
-        if constexpr (SCATTER) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const bool in_x = lane != kWave - 1 && x + j < W - 1; // stencil domain of the reference; lane 63 owns nothing
-            // vertical pairs of the row before (it exists: y0 + r - 1 < y < H, and y - 1 < H - 1)
-            if (r > 0 && in_x && above[j] != cur[j]) flags |= 1u << (4 * R + 4 * (r - 1) + j);
-            const int32_t nr = j < 3 ? cur[(j + 1) & 3] : right;
-            if (r < R && in_x && y < H - 1 && cur[j] != nr) flags |= 1u << (4 * r + j);
-            above[j] = cur[j];
-          }
-        }
       }
     }
   }
@@ -248,9 +304,11 @@ __global__ __launch_bounds__(WAVES * kWave, SCATTER ? DRTK_ONEPASS_WAVES : 1) vo
       // pairs fit, so this phase has no dense form), the table's keys -- initialised after it -- the lanes' verdicts
       static_assert(2 * kCap >= (kWave - 1) * 8 * R && kSlots >= kWave, "the list's storage must hold a strip's pair positions, the keys' one word per lane");
       const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave); // (uniform: the wave's LDS addresses stay in scalar registers)
-      flags = needed_pair_flags<T, R>(
-          flags, lane, sx * (kWave - 1) * VEC, y0, index_img + int64_t(n) * HW, pairs.v_pix + int64_t(n) * pairs.V * 3,
-          pairs.vi + int64_t(n) * pairs.vi_sN, W, reinterpret_cast<uint32_t*>(s_list[wave]), reinterpret_cast<uint32_t*>(t_keys[wave]));
+      // this view's vertex and corner tables, V x 3 floats and F x 3 ids (V, F < 2^32 / 12 on this path, checked by the launcher)
+      const uint32_t v_bytes = static_cast<uint32_t>(pairs.V) * 12u, vi_bytes = static_cast<uint32_t>(pairs.F) * 12u;
+      flags = needed_pair_flags<T, R, DRTK_EDGE_CLASSIFY_ROUNDS>(
+          flags, lane, sx * (kWave - 1) * VEC, y0, idx_rsrc, plane_bytes, buffer_rsrc(pairs.v_pix + int64_t(n) * pairs.V * 3, v_bytes), v_bytes,
+          buffer_rsrc(pairs.vi + int64_t(n) * pairs.vi_sN, vi_bytes), vi_bytes, W, reinterpret_cast<uint32_t*>(s_list[wave]), reinterpret_cast<uint32_t*>(t_keys[wave]));
       if (__ballot(flags != 0) == 0) return; // (wave-uniform) seams only: the host has cleared grad_v_pix, nothing to add
     }
 #endif
@@ -271,16 +329,48 @@ __global__ __launch_bounds__(WAVES * kWave, SCATTER ? DRTK_ONEPASS_WAVES : 1) vo
 #pragma unroll
     for (int j = 0; j < VEC; ++j) ax[r][j] = ay[r][j] = T(0);
 
+  // SCATTER: a lane that loads nothing (load_any) takes the offset beyond the plane for every row
+  uint32_t ch_off[R + 1];
+#pragma unroll
+  for (int r = 0; r <= R; ++r) ch_off[r] = load_any ? row_off[r] : plane_bytes;
   for (int c = 0; c < C; ++c) {
     const T* ip = img_n + int64_t(c) * HW;
     const T* gp = go_n + int64_t(c) * HW;
     Row<T, VEC> ri[R + 1], rg[R + 1];
+    if constexpr (SCATTER) {
+      // The 2 (R + 1) row loads of a channel in ONE round trip, the `next` shuffles after them.  Each load stays inside
+      // plane c of this view's img / grad_output: the descriptors cover exactly its H W elements (c < C), and an element
+      // beyond the end of its row reads 0 through the select below -- as does, by the range check, everything of a row
+      // below the image, of a lane off the canvas and of a lane that needs nothing.
+      const BufferRsrc i_rsrc = buffer_rsrc(ip, plane_bytes), g_rsrc = buffer_rsrc(gp, plane_bytes);
 #pragma unroll
-    for (int r = 0; r <= R; ++r) {
-      const bool y_ok = (y0 + r) < H; // wave-uniform
-      // (round 6: rows 1 .. R-1, read by this wave alone, as non-temporal loads: 0.763 vs 0.750 ms for the fused route -- no)
-      ri[r] = load_row<T, VEC>(ip, int64_t(y0 + r) * W, x, W, x_ok && y_ok, lane);
-      rg[r] = load_row<T, VEC>(gp, int64_t(y0 + r) * W, x, W, x_ok && y_ok, lane);
+      for (int r = 0; r <= R; ++r) {
+        const auto qi = __builtin_amdgcn_raw_buffer_load_b128(i_rsrc, ch_off[r], 0, 0);
+        const auto qg = __builtin_amdgcn_raw_buffer_load_b128(g_rsrc, ch_off[r], 0, 0);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ri[r].v[j] = as_float(qi[j]), rg[r].v[j] = as_float(qg[j]);
+      }
+#pragma unroll
+      for (int r = 0; r <= R; ++r) {
+#pragma unroll
+        for (int j = 1; j < 4; ++j) { // (element 0 lies in its row wherever the lane is on the canvas)
+          ri[r].v[j] = x + j < W ? ri[r].v[j] : T(0);
+          rg[r].v[j] = x + j < W ? rg[r].v[j] : T(0);
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < R; ++r) { // lane 63's is never used: it is the halo lane; nor is row R's
+        ri[r].next = __shfl_down(ri[r].v[0], 1);
+        rg[r].next = __shfl_down(rg[r].v[0], 1);
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r <= R; ++r) {
+        const bool y_ok = (y0 + r) < H; // wave-uniform
+        // (round 6: rows 1 .. R-1, read by this wave alone, as non-temporal loads: 0.763 vs 0.750 ms for the fused route -- no)
+        ri[r] = load_row<T, VEC>(ip, int64_t(y0 + r) * W, x, W, x_ok && y_ok, lane);
+        rg[r] = load_row<T, VEC>(gp, int64_t(y0 + r) * W, x, W, x_ok && y_ok, lane);
+      }
     }
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -423,6 +513,22 @@ struct TriInfo {
   int32_t i0, i1, i2;
 };
 
+// the edge vectors and the doubled area from the three corners' positions (t.i0 .. t.i2 are the caller's)
+template <typename T>
+__device__ __forceinline__ void tri_setup(TriInfo<T>& t, T p0x, T p0y, T p1x, T p1y, T p2x, T p2y) {
+  t.p0x = p0x;
+  t.p0y = p0y;
+  t.p1x = p1x;
+  t.p1y = p1y;
+  t.v01x = t.p1x - t.p0x;
+  t.v01y = t.p1y - t.p0y;
+  t.v02x = p2x - t.p0x;
+  t.v02y = p2y - t.p0y;
+  t.v12x = p2x - t.p1x;
+  t.v12y = p2y - t.p1y;
+  t.den = t.v01x * t.v02y - t.v01y * t.v02x;
+}
+
 template <typename T>
 __device__ __forceinline__ void load_tri(
     const T* __restrict__ v_n, const int32_t* __restrict__ vi_n, int32_t idx, TriInfo<T>& t) {
@@ -432,18 +538,10 @@ __device__ __forceinline__ void load_tri(
     const int32_t* f = vi_n + int64_t(idx) * 3;
     t.i0 = f[0], t.i1 = f[1], t.i2 = f[2];
   }
-  t.p0x = v_n[3 * (int64_t)t.i0 + 0];
-  t.p0y = v_n[3 * (int64_t)t.i0 + 1];
-  t.p1x = v_n[3 * (int64_t)t.i1 + 0];
-  t.p1y = v_n[3 * (int64_t)t.i1 + 1];
+  const T p0x = v_n[3 * (int64_t)t.i0 + 0], p0y = v_n[3 * (int64_t)t.i0 + 1];
+  const T p1x = v_n[3 * (int64_t)t.i1 + 0], p1y = v_n[3 * (int64_t)t.i1 + 1];
   const T p2x = v_n[3 * (int64_t)t.i2 + 0], p2y = v_n[3 * (int64_t)t.i2 + 1];
-  t.v01x = t.p1x - t.p0x;
-  t.v01y = t.p1y - t.p0y;
-  t.v02x = p2x - t.p0x;
-  t.v02y = p2y - t.p0y;
-  t.v12x = p2x - t.p1x;
-  t.v12y = p2y - t.p1y;
-  t.den = t.v01x * t.v02y - t.v01y * t.v02x;
+  tri_setup<T>(t, p0x, p0y, p1x, p1y, p2x, p2y);
 }
 
 // edge_grad_kernel.cu:30-70 : rasterizer's top-left rule on NON-canonical edge functions
@@ -764,6 +862,11 @@ __global__ __launch_bounds__(kBlock) void edge_gather4_kernel(
 // holds one pair A = (px, y), B = A + (1,0) [AXIS 0] or A + (0,1) [AXIS 1] whose indices differ, and the pair's dot
 // term; the wave evaluates its pairs, sums runs of lanes that hit the same two triangles and adds the runs' sums to the
 // vertices through its table.  Wave-collective: called by all lanes of the wave, the idle ones with act = false.
+// Lever of round 10, measured and not kept (profiles/NOTES.md R10): 1 requests a pair's six barycentrics together with its
+// two ids instead of after the evaluation, under the ids' sign.
+#ifndef DRTK_EDGE_BARY_EARLY
+#define DRTK_EDGE_BARY_EARLY 0
+#endif
 template <typename T, int AXIS, int SLOTS>
 __device__ __forceinline__ void scatter_pair_round(
     bool act, int px, int y, T term, const int32_t* __restrict__ idx_n, const T* __restrict__ v_n,
@@ -778,6 +881,10 @@ __device__ __forceinline__ void scatter_pair_round(
     const int64_t pb = AXIS == 0 ? pa + 1 : pa + W;
     ia = idx_n[pa];
     ib = idx_n[pb];
+#if DRTK_EDGE_BARY_EARLY
+    // both pixels of a pair are pixels of this view whatever their ids: the barycentrics are requested with the ids
+    const T ea[3] = {bary_n[pa], bary_n[HW + pa], bary_n[2 * HW + pa]}, eb[3] = {bary_n[pb], bary_n[HW + pb], bary_n[2 * HW + pb]};
+#endif
     TriInfo<T> ta, tb;
     load_tri<T>(v_n, vi_n, ia, ta);
     load_tri<T>(v_n, vi_n, ib, tb);
@@ -786,8 +893,13 @@ __device__ __forceinline__ void scatter_pair_round(
     ga = -gA, za = -zA, gb = -gB, zb = -zB; // edge_grad_kernel.cu:427-445 negates
     va[0] = ta.i0, va[1] = ta.i1, va[2] = ta.i2;
     vb[0] = tb.i0, vb[1] = tb.i1, vb[2] = tb.i2;
+#if DRTK_EDGE_BARY_EARLY
+#pragma unroll
+    for (int k = 0; k < 3; ++k) Ba[k] = ia >= 0 ? ea[k] : T(0), Bb[k] = ib >= 0 ? eb[k] : T(0);
+#else
     if (ia >= 0) Ba[0] = bary_n[pa], Ba[1] = bary_n[HW + pa], Ba[2] = bary_n[2 * HW + pa];
     if (ib >= 0) Bb[0] = bary_n[pb], Bb[1] = bary_n[HW + pb], Bb[2] = bary_n[2 * HW + pb];
+#endif
   }
   // a side takes part if its pixel is foreground and it received something
   const bool a_on = ia >= 0 && (ga != T(0) || za != T(0));
@@ -826,10 +938,14 @@ __device__ __forceinline__ void scatter_pair_round(
 // that a round's index gathers run along image rows) and taken one per lane; a pair with a background pixel is needed
 // without a look at its triangle.  A needed pair sets its bit in its owner's word of `mask` (one word per lane).
 // Wave-collective; `list` and `mask` are wave-private LDS, free for other use on return.
-template <typename T, int R>
+// P rounds of 64 pairs are in flight at a time, and each of a pair's three dependent gathers is issued for all of them
+// before the first is waited for -- the two ids of P pairs, then their two faces, then their six vertices, then the tests:
+// three round trips per 64 P pairs.  The gathers go through descriptors of exactly this view's index plane, corner
+// table and vertex table (idx_bytes, vi_bytes, v_bytes: their sizes, which as an offset mean "nothing to load").
+template <typename T, int R, int P>
 __device__ __forceinline__ uint32_t needed_pair_flags(
-    uint32_t flags, int lane, int strip_x0, int y0, const int32_t* __restrict__ idx_n, const T* __restrict__ v_n,
-    const int32_t* __restrict__ vi_n, int W, uint32_t* list, uint32_t* mask) {
+    uint32_t flags, int lane, int strip_x0, int y0, BufferRsrc idx_rsrc, uint32_t idx_bytes, BufferRsrc v_rsrc,
+    uint32_t v_bytes, BufferRsrc vi_rsrc, uint32_t vi_bytes, int W, uint32_t* list, uint32_t* mask) {
   const unsigned long long lt = (1ull << lane) - 1ull;
   mask[lane] = 0;
   int n_all = 0;
@@ -845,27 +961,64 @@ __device__ __forceinline__ uint32_t needed_pair_flags(
     }
   }
   wave_lds_sync();
-  for (int t0 = 0; t0 < n_all; t0 += kWave) {
-    const int t = t0 + lane;
-    if (t < n_all) {
-      const uint32_t entry = list[t];
-      const int bit = static_cast<int>(entry & 31u), owner = static_cast<int>(entry >> 5);
+  for (int t0 = 0; t0 < n_all; t0 += kWave * P) {
+    bool valid[P], both[P];
+    uint32_t entry[P];
+    int xa[P], ya[P], xb[P], yb[P];
+    int32_t id[P][2], corner[P][2][3];
+    T pos[P][2][3][2];
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+      const int t = t0 + p * kWave + lane;
+      valid[p] = t < n_all;
+      entry[p] = list[valid[p] ? t : 0]; // (entry 0 exists: n_all > 0)
+    }
+    // 1. the two ids.  A listed pair lies in the stencil domain, so both of its pixels are pixels of this view; a lane
+    //    without a pair loads nothing.
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+      const int bit = static_cast<int>(entry[p] & 31u), owner = static_cast<int>(entry[p] >> 5);
       const bool vertical = bit >= 4 * R;
       const int k = vertical ? bit - 4 * R : bit;
-      const int xa = strip_x0 + owner * 4 + (k & 3), ya = y0 + (k >> 2);
-      const int xb = vertical ? xa : xa + 1, yb = vertical ? ya + 1 : ya;
-      const int64_t pa = int64_t(ya) * W + xa;
-      const int32_t ia = idx_n[pa], ib = idx_n[vertical ? pa + W : pa + 1];
-      bool need = true;
-      if (ia >= 0 && ib >= 0) { // `both` of eval_pair
-        TriInfo<T> ta, tb;
-        load_tri<T>(v_n, vi_n, ia, ta);
-        load_tri<T>(v_n, vi_n, ib, tb);
-        const bool a_in_b = pix_in_tri(tb, xa, ya);
-        const bool b_in_a = pix_in_tri(ta, xb, yb);
-        need = a_in_b || b_in_a; // not `adjacent`
+      xa[p] = strip_x0 + owner * 4 + (k & 3), ya[p] = y0 + (k >> 2);
+      xb[p] = vertical ? xa[p] : xa[p] + 1, yb[p] = vertical ? ya[p] + 1 : ya[p];
+      id[p][0] = buffer_load_i32(idx_rsrc, valid[p] ? static_cast<uint32_t>(ya[p] * W + xa[p]) * 4u : idx_bytes);
+      id[p][1] = buffer_load_i32(idx_rsrc, valid[p] ? static_cast<uint32_t>(yb[p] * W + xb[p]) * 4u : idx_bytes);
+    }
+    // 2. the two faces of a pair of two foreground pixels (`both` of eval_pair); an id that is no triangle of this view
+    //    lies beyond the corner table and reads the corners 0, 0, 0
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+      both[p] = valid[p] && id[p][0] >= 0 && id[p][1] >= 0;
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const auto f = __builtin_amdgcn_raw_buffer_load_b96(vi_rsrc, both[p] ? static_cast<uint32_t>(id[p][s]) * 12u : vi_bytes, 0, 0);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) corner[p][s][k] = static_cast<int32_t>(f[k]);
       }
-      if (need) atomicOr(&mask[owner], 1u << bit);
+    }
+    // 3. x and y of the six vertices; a corner that is no vertex of this view lies beyond the vertex table and reads 0, 0
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          const auto xy = __builtin_amdgcn_raw_buffer_load_b64(v_rsrc, both[p] ? static_cast<uint32_t>(corner[p][s][k]) * 12u : v_bytes, 0, 0);
+          pos[p][s][k][0] = as_float(xy[0]), pos[p][s][k][1] = as_float(xy[1]);
+        }
+      }
+    }
+    // 4. the tests of eval_pair
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+      TriInfo<T> ta, tb;
+      tri_setup<T>(ta, pos[p][0][0][0], pos[p][0][0][1], pos[p][0][1][0], pos[p][0][1][1], pos[p][0][2][0], pos[p][0][2][1]);
+      tri_setup<T>(tb, pos[p][1][0][0], pos[p][1][0][1], pos[p][1][1][0], pos[p][1][1][1], pos[p][1][2][0], pos[p][1][2][1]);
+      const bool a_in_b = pix_in_tri(tb, xa[p], ya[p]);
+      const bool b_in_a = pix_in_tri(ta, xb[p], yb[p]);
+      const bool need = valid[p] && (!both[p] || a_in_b || b_in_a); // not `adjacent`
+      if (need) atomicOr(&mask[entry[p] >> 5], 1u << (entry[p] & 31u));
     }
   }
   wave_lds_sync();
@@ -1149,14 +1302,17 @@ int edge_grad_backward_fused_impl(
   }
 #if DRTK_EDGE_ONEPASS
   if constexpr (std::is_same<T, float>::value) {
-    if (edge_onepass_wanted(N * HW)) {
+    // (the one-pass kernel addresses a view's planes and tables with 32-bit byte offsets; a view beyond that -- a gigapixel,
+    // 357 M vertices or triangles -- takes the two kernels, which address with pointers)
+    const bool addressable = HW <= (int64_t(1) << 30) - 8 && V < (int64_t(1) << 32) / 12 && F < (int64_t(1) << 32) / 12;
+    if (edge_onepass_wanted(N * HW) && addressable) {
       // one pass: edge_dots_kernel scatters its own pairs (SCATTER); the workspace is not touched.  grad_v_pix is cleared by
       // a launch of its own: spread over the grid of the scattering kernel the fill would race other workgroups' atomics.
       if (N * V > 0 && fill_bytes_async(grad_v_pix, 0, sizeof(T) * N * V * 3, stream) != DRTK_OK) return DRTK_ERR_LAUNCH;
       const int strips_x = static_cast<int>(ceil_div(W, (kWave - 1) * 4)); // lane 63 = halo
       const int bands_y = static_cast<int>(ceil_div(H, kStripRows * kDotsWaves));
       const dim3 grid(static_cast<unsigned>(int64_t(strips_x) * bands_y), static_cast<unsigned>(N));
-      const PairArgs<T> pairs{v_pix, vi, bary_img, grad_v_pix, V, vi_sN, static_cast<T>(max_dp_dr)};
+      const PairArgs<T> pairs{v_pix, vi, bary_img, grad_v_pix, V, vi_sN, F, static_cast<T>(max_dp_dr)};
       DRTK_LAUNCH((edge_dots_kernel<T, 4, kStripRows, kDotsWaves, true>), grid, dim3(kDotsWaves * kWave), 0, stream, img, grad_output, index_img, (int)C, (int)H, (int)W, strips_x, static_cast<T*>(nullptr), static_cast<T*>(nullptr), xcd_strip(int64_t(strips_x) * (16 / (kStripRows * kDotsWaves))), static_cast<T*>(nullptr), int64_t(0), pairs);
       DRTK_RETURN_IF_LAUNCH_FAILED();
       return DRTK_OK;
