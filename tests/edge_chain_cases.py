@@ -19,7 +19,7 @@ for p in (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
 
 from test_gpu_edge_onepass import STRIP_H, STRIP_W, _case, _mesh, _strip_pairs  # noqa: E402,F401  (the strip geometry of the kernel, not restated)
 
-ROUNDS = 2  # DRTK_EDGE_CLASSIFY_ROUNDS: rounds of 64 pairs the classification keeps in flight
+ROUNDS = 2  # kClassifyRounds of edge_grad.hip: rounds of 64 pairs the classification keeps in flight
 WIDTHS = (1, 2, 3, 5, 6, 254, 506)  # W % 4 = 2, W < 4, and the same past one and two strips
 HEIGHTS = (1, 2, 3, 9)
 CHANNELS = (1, 3, 16)
