@@ -7,12 +7,13 @@
 // wave-level run reduction of segscatter.hpp in chunks of 16 channels (3*16 = 48 of the wave's 64
 // lanes own one (corner, channel) pair each), replacing the reference's per-channel
 // WarpReduce + __syncthreads + atomics loop.
+#include <string>
+
 #include "common.hpp"
 #include "segscatter.hpp"
 
 namespace drtk_amd {
 namespace {
-
 
 template <typename T>
 struct Vec4;
@@ -39,12 +40,7 @@ struct Vec4<double> {
 // element's alignment only, and the last lane of a view whose pixel count is not a multiple of four goes pixel by pixel
 // (round 4; before, such images took one pixel per lane: 1.2x the time at 2048 x 2046).
 // (round 6: bounded to 4 waves per SIMD -- 128 registers -- the prefetching instantiation spills 30-38 of its 158)
-#ifndef DRTK_INTERP_FWD_DIAG
-#define DRTK_INTERP_FWD_DIAG 0 // 1 / 2: diagnostic builds of the prefetching forward kernel (profiles/NOTES.md R6.12); never the product
-#endif
-#ifndef DRTK_INTERP_FWD_NT
-#define DRTK_INTERP_FWD_NT 1 // index / barycentric quads as non-temporal loads: read once (0.524 -> 0.508 ms, four interleaved rounds on one box, round 6)
-#endif
+// The index / barycentric quads of the aligned four-pixel lane are non-temporal loads: each is read once (profiles/NOTES.md R12).
 template <typename T, int VEC, int CV, bool PREFETCH = false, bool ANYW = false>
 __global__ __launch_bounds__(kBlock) void interpolate_kernel(
     const T* __restrict__ attrs, const int32_t* __restrict__ vi,
@@ -86,17 +82,9 @@ __global__ __launch_bounds__(kBlock) void interpolate_kernel(
       }
     }
   } else if constexpr (VEC == 4) {
-#if DRTK_INTERP_FWD_NT
     const NtQuad<int32_t> t4 = nt_load4(idx_p);
     tr[0] = t4.x, tr[1] = t4.y, tr[2] = t4.z, tr[3] = t4.w;
     const NtQuad<T> a = nt_load4(bary_p), b = nt_load4(bary_p + HW), c = nt_load4(bary_p + 2 * HW);
-#else
-    const int4 t4 = *reinterpret_cast<const int4*>(idx_p);
-    tr[0] = t4.x, tr[1] = t4.y, tr[2] = t4.z, tr[3] = t4.w;
-    const V4 a = *reinterpret_cast<const V4*>(bary_p);
-    const V4 b = *reinterpret_cast<const V4*>(bary_p + HW);
-    const V4 c = *reinterpret_cast<const V4*>(bary_p + 2 * HW);
-#endif
     B0[0] = a.x, B0[1] = a.y, B0[2] = a.z, B0[3] = a.w;
     B1[0] = b.x, B1[1] = b.y, B1[2] = b.z, B1[3] = b.w;
     B2[0] = c.x, B2[1] = c.y, B2[2] = c.z, B2[3] = c.w;
@@ -176,13 +164,8 @@ __global__ __launch_bounds__(kBlock) void interpolate_kernel(
 #pragma unroll
       for (int j = 0; j < VEC; ++j) {
         if (tr[j] != -1) {
-#if DRTK_INTERP_FWD_DIAG == 2 // (diagnostic build: no attribute gathers -- the stream alone)
-#pragma unroll
-          for (int k = 0; k < 3; ++k) q[j][k] = V4{B0[j], B1[j], B2[j], T(c0 + k)};
-#else
 #pragma unroll
           for (int k = 0; k < 3; ++k) q[j][k] = *reinterpret_cast<const V4*>(attrs_n + off[j][k] + c0);
-#endif
         }
       }
     };
@@ -205,11 +188,7 @@ __global__ __launch_bounds__(kBlock) void interpolate_kernel(
       }
 #pragma unroll
       for (int cc = 0; cc < CV; ++cc) {
-#if DRTK_INTERP_FWD_DIAG == 1 // (diagnostic build: the planes are computed and not stored -- reads and gathers alone)
-        if (r[cc][0] == T(123456.75) && r[cc][3] == T(-98765.25)) store4(out_p + int64_t(c0 + cc) * HW, r[cc][0], r[cc][1], r[cc][2], r[cc][3]);
-#else
         store4(out_p + int64_t(c0 + cc) * HW, r[cc][0], r[cc][1], r[cc][2], r[cc][3]);
-#endif
       }
 #pragma unroll
       for (int j = 0; j < VEC; ++j) {
@@ -561,36 +540,6 @@ __global__ __launch_bounds__(kBlock) void interpolate_backward_small_kernel(
 //     the end.  Per-run atomics are what the counters show as write traffic beyond bary_grad (864 MB against 403 MB at
 //     the bench shape), and on rows that are not a multiple of 64 bytes (C = 12, 24) they are several times slower still.
 //     A vertex that finds no slot keeps the direct atomics.
-#ifndef DRTK_INTERP_WIDE_ONLY
-#define DRTK_INTERP_WIDE_ONLY false
-#endif
-#ifndef DRTK_INTERP_ANYC_QA
-#define DRTK_INTERP_ANYC_QA 1
-#endif
-#ifndef DRTK_INTERP_ANYC_SPLIT
-#define DRTK_INTERP_ANYC_SPLIT 1
-#endif
-#ifndef DRTK_INTERP_ANYC_WAVES
-#define DRTK_INTERP_ANYC_WAVES 4
-#endif
-#ifndef DRTK_INTERP_CH8
-#define DRTK_INTERP_CH8 1
-#endif
-#ifndef DRTK_INTERP_CH12
-#define DRTK_INTERP_CH12 1
-#endif
-#ifndef DRTK_INTERP_CH12_MAXC
-#define DRTK_INTERP_CH12_MAXC 12
-#endif
-#ifndef DRTK_INTERP_CH8_ANYC
-#define DRTK_INTERP_CH8_ANYC 0 // 9 <= C <= 15, C % 4 != 0: chunks of 8 + a tail (4 waves per SIMD) instead of one chunk (3)
-#endif
-#ifndef DRTK_INTERP_CH8_WAVES
-#define DRTK_INTERP_CH8_WAVES 4 // (with the bary gradient 104 VGPRs; 4-12 spilled at 5)
-#endif
-#ifndef DRTK_INTERP_F64_WAVES
-#define DRTK_INTERP_F64_WAVES 3 // waves per SIMD the double instantiations are compiled for (144-152 VGPRs; 32-50 spilled at 4)
-#endif
 //   * ANYC (round 5): channel counts that are not a multiple of four (C >= 5: position + normal = 6, RGB + k features) and
 //     attribute tensors that are only element-aligned.  The last chunk is then 1 ... 15 channels: its grad_out planes are
 //     still fetched in groups of four, the planes beyond C through a descriptor of ZERO records (they read 0.0 without
@@ -599,12 +548,19 @@ __global__ __launch_bounds__(kBlock) void interpolate_backward_small_kernel(
 //     channels the previous group already took; phase 2 is channel-count agnostic (J = 3 cc lanes).  Rows of such a C
 //     are never whole 64-byte segments, so the run sums go through the workgroup's vertex table.
 //   * double (round 5): the same pipeline in chunks of CH = 8 channels (the registers of 16 floats), 8-byte buffer loads.
-#ifndef DRTK_INTERP_BWD_AUX
-#define DRTK_INTERP_BWD_AUX 2 // cache policy of the grad_out / bary plane loads: 2 = nt (each plane is read once per launch: 0.600 -> 0.581 ms
-                               // at C = 16, same box, round 6; 0 = default policy)
-#endif
+// Waves per SIMD the wide kernel is compiled for: 4 (128 VGPRs) for every float flavour -- the chunk of 12 takes 104 with the bary
+// gradient and spills 4-12 at 5 --, 3 for double (144-152 VGPRs; 32-50 spilled at 4).
+constexpr int kWideWaves = 4;
+constexpr int kWideWavesF64 = 3;
+// Cache policy of the grad_out / bary plane loads: 2 = nt, each plane is read once per launch (0 = the default policy was slower).
+constexpr int kPlaneLoadAux = 2;
+// Groups of four attribute channels per corner requested BEFORE phase 2 (the rest after it): with ANYC and the bary gradient more
+// than one spills at 4 waves per SIMD.
+constexpr int kAttrGroupsAhead = 1;
+// ANYC, 16-channel chunks: the last group is requested only after the products of the others (124 instead of 138 VGPRs: 4 waves).
+constexpr bool kAnycSplitLastGroup = true;
 template <typename T, bool HAS_BARY, bool TABLE, int CH, bool ANYC>
-__global__ __launch_bounds__(kBlock, (sizeof(T) == 8 ? DRTK_INTERP_F64_WAVES : CH == 8 || CH == 12 ? DRTK_INTERP_CH8_WAVES : ANYC && HAS_BARY ? DRTK_INTERP_ANYC_WAVES : 4)) void interpolate_backward_wide_kernel(
+__global__ __launch_bounds__(kBlock, (sizeof(T) == 8 ? kWideWavesF64 : kWideWaves)) void interpolate_backward_wide_kernel(
     const T* __restrict__ grad_out, const T* __restrict__ attrs, const int32_t* __restrict__ vi,
     const int32_t* __restrict__ index_img, const T* __restrict__ bary_img, int64_t V, int C,
     int64_t vi_sN, int H, int W, int tiles_x, T* __restrict__ attr_grad, T* __restrict__ bary_grad,
@@ -699,9 +655,9 @@ __global__ __launch_bounds__(kBlock, (sizeof(T) == 8 ? DRTK_INTERP_F64_WAVES : C
   auto plane_load = [&](const T* plane, uint32_t byte_offset, bool exists) -> T { // `exists`: wave-uniform (ANYC: a plane < C)
     const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(plane), 0, exists ? static_cast<int>(plane_bytes) : 0, 0x00020000);
     if constexpr (sizeof(T) == 4) {
-      return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b32(r, byte_offset, 0, DRTK_INTERP_BWD_AUX));
+      return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b32(r, byte_offset, 0, kPlaneLoadAux));
     } else {
-      return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b64(r, byte_offset, 0, DRTK_INTERP_BWD_AUX));
+      return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b64(r, byte_offset, 0, kPlaneLoadAux));
     }
   };
   auto row_offset = [&](int ps) -> uint32_t { // beyond the plane for a lane off the canvas
@@ -794,14 +750,8 @@ __global__ __launch_bounds__(kBlock, (sizeof(T) == 8 ? DRTK_INTERP_F64_WAVES : C
     const T* a0 = attrs_n + int64_t(v0) * C + c0;
     const T* a1 = attrs_n + int64_t(v1) * C + c0;
     const T* a2 = attrs_n + int64_t(v2) * C + c0;
-#ifndef DRTK_INTERP_QA
-#define DRTK_INTERP_QA 1
-#endif
-    // float4 per corner requested before / after phase 2 (ANYC + bary gradient: the window arithmetic of the partial group spills
-    // 4-10 registers at 4 waves per SIMD, and 2-4 with every request moved behind phase 2; rounds 5a-b ran it at 3 waves, 138
-    // registers.  With the LAST group of a 16-channel chunk requested after the products of the others -- DRTK_INTERP_ANYC_SPLIT,
-    // below -- it is 124 registers and runs at 4: C = 13 ... 15 0.855 -> 0.745 ms, 17 1.19 -> 1.05, 21 1.27 -> 1.12, 37 1.90 -> 1.65)
-    constexpr int QA = ANYC ? DRTK_INTERP_ANYC_QA : DRTK_INTERP_QA, QD = CH / 4 - QA;
+    // float4 per corner requested before / after phase 2 (kAttrGroupsAhead, kAnycSplitLastGroup: profiles/NOTES.md R12)
+    constexpr int QA = kAttrGroupsAhead, QD = CH / 4 - QA;
     // group q of a row's chunk: channels 4q .. 4q+3, or (ANYC, the chunk's partial last group) the four that end the row
     typedef T TQuadU __attribute__((ext_vector_type(4), aligned(sizeof(T))));
     auto attr4 = [&](const T* row, int q) -> V4 {
@@ -854,7 +804,7 @@ __global__ __launch_bounds__(kBlock, (sizeof(T) == 8 ? DRTK_INTERP_F64_WAVES : C
       const T* sg = s_g[wave];
       const T* sb = s_b[wave];
       // (the table + bary variant sits at its register bound: it keeps the unpipelined reads)
-      scatter_runs_rows<T, TableAcc, DRTK_INTERP_WIDE_ONLY, TABLE, 16, !(TABLE && HAS_BARY)>(
+      scatter_runs_rows<T, TableAcc, /*WIDE_ONLY=*/false, TABLE, 16, !(TABLE && HAS_BARY)>(
           heads, cov, TABLE ? s_slot[wave] : nullptr, s_vid[wave], 3 * cc, cc, t_vals, C, attr_grad_n, CG, c0, sg, sb, dbg,
           TABLE ? c0 : 0);
     }
@@ -870,7 +820,7 @@ __global__ __launch_bounds__(kBlock, (sizeof(T) == 8 ? DRTK_INTERP_F64_WAVES : C
         const T* d2 = attrs_n + int64_t(w2) * C + c0;
         // (ANYC at four waves per SIMD: the last group is requested only after the products of the others -- twelve registers
         // less in flight, one more round trip per chunk)
-        constexpr int QD1 = (ANYC && CH == 16 && DRTK_INTERP_ANYC_SPLIT && QD > 1) ? QD - 1 : QD; // (12-channel chunks fit without: 0.69 vs 0.71 ms at C = 11)
+        constexpr int QD1 = (ANYC && CH == 16 && kAnycSplitLastGroup && QD > 1) ? QD - 1 : QD; // (12-channel chunks fit without: 0.69 vs 0.71 ms at C = 11)
 #pragma unroll
         for (int q = 0; q < QD1; ++q) {
           if (4 * (QA + q) < cc) {
@@ -963,6 +913,89 @@ __global__ __launch_bounds__(kBlock) void compact_rows_kernel(const T* __restric
   out[i] = ws[r * CG + (i - r * C)];
 }
 
+// ---- launching -----------------------------------------------------------------------------------------------------------------
+// The timing report names a launch by the text of its DRTK_LAUNCH site (common.hpp).  The launch helpers of this file are
+// templates, whose sites would spell the parameters' names; they name the instantiation by its VALUES instead, T as every site
+// spells it -- "interpolate_backward_wide_kernel<T, true, false, 16, false>" -- so that the report says which kernel ran
+// (tests/test_gpu_scatter_tables.py and tests/test_gpu_interpolate_routes.py read the route from it).  These names are NOT the
+// text a DRTK_LAUNCH site would give: no parentheses around them, a chunk is its number, defaulted arguments are written out.
+// Readers take the name up to '<' or split the arguments at the commas.
+inline void append_value(std::string& s, bool v) { s += v ? "true" : "false"; }
+inline void append_value(std::string& s, int v) { s += std::to_string(v); }
+template <auto... ARGS>
+std::string instance_name(const char* kernel) {
+  std::string s = std::string(kernel) + "<T";
+  ((s += ", ", append_value(s, ARGS)), ...);
+  return s + ">";
+}
+// one launch of `kernel` under that name (a string that lives as long as the library): what DRTK_LAUNCH does with its site's text
+template <typename... P, typename... A>
+void launch_as(const std::string& name, void (*kernel)(P...), dim3 grid, size_t lds, hipStream_t stream, A... args) {
+  KernelTimingScope timing(name.c_str(), stream);
+  hipLaunchKernelGGL(kernel, grid, dim3(kBlock), lds, stream, static_cast<P>(args)...);
+}
+
+// ---- forward -------------------------------------------------------------------------------------------------------------------
+// double never prefetches: the prefetching loop needs 254 VGPRs there -- one wave per SIMD -- and loses to the plain one at two
+template <typename T>
+constexpr bool kForwardPrefetch = sizeof(T) == 4;
+
+template <typename T>
+struct ForwardCall {  // the entry point's arguments
+  const T* attrs;
+  const int32_t *vi, *index_img;
+  const T* bary_img;
+  int64_t N, V, C, vi_sN, H, W;
+  T* out;
+  int zero_background;
+  hipStream_t stream;
+};
+
+template <typename T, int VEC, int CV, bool PREFETCH, bool ANYW>
+void launch_forward(const ForwardCall<T>& c) {
+  static const std::string name = instance_name<VEC, CV, PREFETCH, ANYW>("interpolate_kernel");
+  launch_as(
+      name, interpolate_kernel<T, VEC, CV, PREFETCH, ANYW>,
+      dim3(static_cast<unsigned>(ceil_div(ceil_div(c.H * c.W, VEC), kBlock)), static_cast<unsigned>(c.N)), 0, c.stream, c.attrs, c.vi,
+      c.index_img, c.bary_img, c.V, (int)c.C, c.vi_sN, (int)c.H, (int)c.W, c.out, c.zero_background,
+      xcd_strip(ceil_div(16 * c.W, int64_t(kBlock) * VEC)));
+}
+// CV and PREFETCH of a (VEC, ANYW) pair; the prefetching loop exists for four pixels x four channels of float only
+template <typename T, int VEC, bool ANYW>
+void launch_forward_channels(const ForwardCall<T>& c, bool cvec, bool prefetch) {
+  if constexpr (VEC == 4 && kForwardPrefetch<T>) {
+    if (prefetch) return launch_forward<T, 4, 4, true, ANYW>(c);
+  }
+  if (cvec) launch_forward<T, VEC, 4, false, ANYW>(c); else launch_forward<T, VEC, 1, false, ANYW>(c);
+}
+
+template <typename T>
+int interpolate_impl(
+    const T* attrs, const int32_t* vi, const int32_t* index_img, const T* bary_img, int64_t N,
+    int64_t V, int64_t C, int64_t vi_sN, int64_t H, int64_t W, T* out, int zero_background, hipStream_t stream) {
+  if (N * H * W * C == 0) return DRTK_OK;
+  // whole 16-byte aligned quads of pixels: W % 4 == 0 and aligned images
+  const bool pvec = (W % 4 == 0) && (reinterpret_cast<uintptr_t>(index_img) % 16 == 0) &&
+      (reinterpret_cast<uintptr_t>(bary_img) % (4 * sizeof(T)) == 0) &&
+      (reinterpret_cast<uintptr_t>(out) % (4 * sizeof(T)) == 0);
+  // the four template arguments:
+  const int vec = pvec || W >= 4 ? 4 : 1;  // VEC: pixels per lane
+  const bool anyw = !pvec && W >= 4;       // ANYW: widths that are not a multiple of four, views into flat buffers
+  const bool cvec = (C % 4 == 0) && (reinterpret_cast<uintptr_t>(attrs) % (4 * sizeof(T)) == 0);  // CV = 4: attribute rows as vectors
+  // PREFETCH: more than one channel vector, and 32-bit row offsets in the prefetching loop
+  const bool prefetch = kForwardPrefetch<T> && vec == 4 && cvec && C > 4 && V * C < (int64_t(1) << 31);
+  const ForwardCall<T> c{attrs, vi, index_img, bary_img, N, V, C, vi_sN, H, W, out, zero_background, stream};
+  if (anyw)
+    launch_forward_channels<T, 4, true>(c, cvec, prefetch);
+  else if (vec == 4)
+    launch_forward_channels<T, 4, false>(c, cvec, prefetch);
+  else
+    launch_forward_channels<T, 1, false>(c, cvec, false);
+  DRTK_RETURN_IF_LAUNCH_FAILED();
+  return DRTK_OK;
+}
+
+// ---- backward: the routing plan ------------------------------------------------------------------------------------------------
 // elements between the rows of the padded gradient workspace: whole 64-byte segments
 template <typename T>
 inline int64_t padded_row(int64_t C) {
@@ -975,48 +1008,139 @@ inline bool rows_are_segments(int64_t C) {
   return row_bytes % 64 == 0 || 64 % row_bytes == 0;
 }
 
+// The thresholds of the rule; the measurements behind each are in profiles/NOTES.md R12.
+// tests/scatter_table_cases.py builds its index images from five of them and reads them from this file BY SPELLING: the three
+// macros below, and the literals of `int log2_slots = ...` and `table = log2_slots >= ...` in plan_backward.  Plain constants,
+// not switches: nothing tests for a definition from outside.
+// The register scan beats the wide pipeline while 3 C products per lane are few (the wide phase 2 keeps 3 C of 64 lanes busy).
+#define DRTK_INTERP_SMALL_MAXC_F32 10
+#define DRTK_INTERP_SMALL_MAXC_F64 7
 template <typename T>
-int interpolate_impl(
-    const T* attrs, const int32_t* vi, const int32_t* index_img, const T* bary_img, int64_t N,
-    int64_t V, int64_t C, int64_t vi_sN, int64_t H, int64_t W, T* out, int zero_background, hipStream_t stream) {
-  const int64_t HW = H * W;
-  if (N * HW * C == 0) return DRTK_OK;
-  const bool pvec = (W % 4 == 0) && (reinterpret_cast<uintptr_t>(index_img) % 16 == 0) &&
-      (reinterpret_cast<uintptr_t>(bary_img) % (4 * sizeof(T)) == 0) &&
-      (reinterpret_cast<uintptr_t>(out) % (4 * sizeof(T)) == 0);
-  const bool cvec = (C % 4 == 0) && (reinterpret_cast<uintptr_t>(attrs) % (4 * sizeof(T)) == 0);
-  const dim3 block(kBlock);
-#define LAUNCH(VEC, CV, ...)                                                                    \
-  DRTK_LAUNCH(                                                                           \
-      (interpolate_kernel<T, VEC, CV, ##__VA_ARGS__>),                                          \
-      dim3(static_cast<unsigned>(ceil_div(ceil_div(HW, VEC), kBlock)), static_cast<unsigned>(N)), block, \
-      0, stream, attrs, vi, index_img, bary_img, V, (int)C, vi_sN, (int)H, (int)W, out, zero_background, \
-      xcd_strip(ceil_div(16 * W, int64_t(kBlock) * VEC)))
-  // (double: the prefetching loop needs 254 VGPRs -- one wave per SIMD -- and loses to the plain one at two: 1.26 vs
-  // 1.15 ms at 8 x 2048^2, C = 16, same box)
-#ifndef DRTK_INTERP_F64_PREFETCH
-#define DRTK_INTERP_F64_PREFETCH 0
-#endif
-  const bool prefetch = sizeof(T) == 4 || DRTK_INTERP_F64_PREFETCH;
-  if (pvec && cvec && C > 4 && V * C < (int64_t(1) << 31) && prefetch) // (32-bit row offsets in the prefetching loop)
-    LAUNCH(4, 4, true);
-  else if (pvec && cvec)
-    LAUNCH(4, 4);
-  else if (pvec)
-    LAUNCH(4, 1);
-  else if (W >= 4 && cvec && C > 4 && V * C < (int64_t(1) << 31) && prefetch) // widths that are not a multiple of four, views into flat buffers
-    LAUNCH(4, 4, true, true);
-  else if (W >= 4 && cvec)
-    LAUNCH(4, 4, false, true);
-  else if (W >= 4)
-    LAUNCH(4, 1, false, true);
-  else if (cvec)
-    LAUNCH(1, 4);
+constexpr int kSmallMaxC = sizeof(T) == 4 ? DRTK_INTERP_SMALL_MAXC_F32 : DRTK_INTERP_SMALL_MAXC_F64;
+// Channel counts the register scan is instantiated for; the bary gradient alone (no scatter) takes it up to here.
+constexpr int kSmallInstMaxC = 12;
+// double rows that are not 32-byte aligned (C % 4 != 0) stay with the register scan up to here: 9 measured, 10 / 11 by the trend.
+constexpr int kSmallMaxCF64Unaligned = 11;
+static_assert(kSmallMaxC<float> <= kSmallInstMaxC && kSmallMaxC<double> <= kSmallInstMaxC && kSmallMaxCF64Unaligned <= kSmallInstMaxC, "instantiated channel counts");
+// Channels per round of the wide pipeline: 16 floats, or their registers' worth of doubles.
+template <typename T>
+constexpr int kWideChunk = sizeof(T) == 4 ? 16 : 8;
+// float, element-aligned rows of 9 ... 12 channels with the bary gradient: ONE chunk of 12 (the 16-channel chunk's registers put
+// that flavour at 3 waves per SIMD).
+constexpr int kChunk12AboveC = 8;
+constexpr int kChunk12MaxC = 12;
+// Padded rows pay while the row is one chunk; with a tail chunk the table, which merges a vertex's chunks, wins.
+constexpr int kPadMaxC = 16;
+// The workgroup's vertex table: as many slots as fit this much LDS (the staging rows take 27 KB; 4 workgroups per CU leave 40 KB
+// each), at most 2^7, and used from 2^4 -- below that, per-run atomics (the two literals in plan_backward).
+#define DRTK_INTERP_TABLE_BYTES 12800
+
+enum class BackwardRoute { kScan, kWide, kGeneric };
+struct BackwardPlan {
+  BackwardRoute route = BackwardRoute::kGeneric;
+  // kWide: the run sums go through the workgroup's table of 2^log2_slots vertices (lds bytes) / into workspace rows padded to CG
+  // elements, compacted afterwards; channels per round
+  bool table = false, padded = false;
+  int chunk = 0, log2_slots = 0, CG = 0;
+  size_t lds = 0;
+  // kGeneric: channels per attribute load, channels per round
+  int cv = 1, generic_chunk = 16;
+};
+
+// Which kernel the backward launches, and how.  cvec: C % 4 == 0 and 16-byte (double: 32-byte) aligned attributes; ws_usable: a
+// workspace is there and holds N V padded rows.  force_generic / no_table: the profiling build's flags 128 / 4096 (false in the
+// product).
+//   * register scan (interpolate_backward_small_kernel) for few channels,
+//   * else the wide pipeline wherever the vertex gradient is wanted (any C >= 5, float and double; 32-bit byte offsets into a
+//     plane), its run sums going -- rows of whole 64-byte segments: straight to global memory; other rows of one chunk, both
+//     gradients, float, with a workspace: to PADDED rows, which then are such segments; other rows otherwise: through the table,
+//   * else the generic kernel: the bary gradient alone beyond the register scan's counts (no scatter, covered pixels only: 0.95 of
+//     the HBM peak), planes of 4 GB and more.
+template <typename T>
+BackwardPlan plan_backward(int64_t C, int64_t HW, bool want_attr, bool want_bary, bool cvec, bool ws_usable, bool force_generic, bool no_table) {
+  BackwardPlan p;
+  p.CG = static_cast<int>(C);
+  const bool small_c = C <= kSmallMaxC<T> || (!want_attr && C <= kSmallInstMaxC) || (sizeof(T) == 8 && C % 4 != 0 && C <= kSmallMaxCF64Unaligned);
+  if (force_generic || (!small_c && !(want_attr && HW * int64_t(sizeof(T)) < (int64_t(1) << 32)))) {
+    p.route = BackwardRoute::kGeneric;
+    // (attributes only: no attribute row is read; C <= 4 keeps a wave-private table, beyond it the run sums go to global memory)
+    p.cv = cvec && want_bary ? 4 : 1;
+    p.generic_chunk = want_attr && C <= 4 ? 4 : 16;
+  } else if (small_c) {
+    p.route = BackwardRoute::kScan;
+  } else {
+    p.route = BackwardRoute::kWide;
+    p.padded = ws_usable && !rows_are_segments<T>(C) && want_bary && sizeof(T) == 4 && C <= kPadMaxC;
+    if (p.padded) p.CG = static_cast<int>(padded_row<T>(C));
+    int log2_slots = 7;
+    while (log2_slots > 0 && (sizeof(TableAcc) * C + 4) * (size_t(1) << log2_slots) > DRTK_INTERP_TABLE_BYTES) --log2_slots;
+    p.log2_slots = log2_slots;
+    // on rows of whole segments the table's lookups and barriers cost more than the fire-and-forget atomics they replace
+    p.table = log2_slots >= 4 && !p.padded && !rows_are_segments<T>(C) && !no_table;
+    p.lds = p.table ? (sizeof(TableAcc) * C + 4) * (size_t(1) << p.log2_slots) : 0;
+    const bool chunk12 = sizeof(T) == 4 && !cvec && C > kChunk12AboveC && C <= kChunk12MaxC && want_bary;
+    p.chunk = chunk12 ? 12 : kWideChunk<T>;
+  }
+  return p;
+}
+
+// ---- backward: launching what the plan says ------------------------------------------------------------------------------------
+template <typename T>
+struct BackwardCall {  // what the three kernels share: their arguments in the kernels' order and types, the grid of 64 x 16 tiles
+  const T *grad_out, *attrs;
+  const int32_t *vi, *index_img;
+  const T* bary_img;
+  int64_t V;
+  int C;
+  int64_t vi_sN;
+  int H, W, tiles_x;
+  T *attr_grad, *bary_grad;
+  int strip;
+  dim3 grid;
+  hipStream_t stream;
+};
+
+template <typename T, bool HAS_VERT, bool HAS_BARY, int CN>
+void launch_scan(const BackwardCall<T>& c) {
+  static const std::string name = instance_name<HAS_VERT, HAS_BARY, CN>("interpolate_backward_small_kernel");
+  launch_as(
+      name, interpolate_backward_small_kernel<T, HAS_VERT, HAS_BARY, CN>, c.grid, 0, c.stream, c.grad_out, c.attrs, c.vi, c.index_img,
+      c.bary_img, c.V, c.vi_sN, c.H, c.W, c.tiles_x, c.attr_grad, c.bary_grad, c.strip);
+}
+// the instantiation of c.C, 1 ... kSmallInstMaxC
+template <typename T, bool HAS_VERT, bool HAS_BARY, int CN = kSmallInstMaxC>
+void launch_scan_channels(const BackwardCall<T>& c) {
+  if (c.C == CN)
+    launch_scan<T, HAS_VERT, HAS_BARY, CN>(c);
+  else if constexpr (CN > 1)
+    launch_scan_channels<T, HAS_VERT, HAS_BARY, CN - 1>(c);
+}
+
+template <typename T, bool HAS_BARY, bool TABLE, int CH, bool ANYC>
+void launch_wide(const BackwardCall<T>& c, const BackwardPlan& p, T* grad_dst) {
+  static const std::string name = instance_name<HAS_BARY, TABLE, CH, ANYC>("interpolate_backward_wide_kernel");
+  launch_as(
+      name, interpolate_backward_wide_kernel<T, HAS_BARY, TABLE, CH, ANYC>, c.grid, p.lds, c.stream, c.grad_out, c.attrs, c.vi,
+      c.index_img, c.bary_img, c.V, c.C, c.vi_sN, c.H, c.W, c.tiles_x, grad_dst, c.bary_grad, debug_flags(), c.strip, p.log2_slots, p.CG);
+}
+// TABLE and CH of a (HAS_BARY, ANYC) pair; the chunk of 12 exists for float with the bary gradient on element-aligned rows only
+template <typename T, bool HAS_BARY, bool ANYC>
+void launch_wide_chunk(const BackwardCall<T>& c, const BackwardPlan& p, T* grad_dst) {
+  if constexpr (sizeof(T) == 4 && HAS_BARY && ANYC) {
+    if (p.chunk == 12) return p.table ? launch_wide<T, HAS_BARY, true, 12, ANYC>(c, p, grad_dst) : launch_wide<T, HAS_BARY, false, 12, ANYC>(c, p, grad_dst);
+  }
+  if (p.table)
+    launch_wide<T, HAS_BARY, true, kWideChunk<T>, ANYC>(c, p, grad_dst);
   else
-    LAUNCH(1, 1);
-#undef LAUNCH
-  DRTK_RETURN_IF_LAUNCH_FAILED();
-  return DRTK_OK;
+    launch_wide<T, HAS_BARY, false, kWideChunk<T>, ANYC>(c, p, grad_dst);
+}
+
+template <typename T, bool HAS_VERT, bool HAS_BARY, int CV, int CHUNK>
+void launch_generic(const BackwardCall<T>& c) {
+  static const std::string name = instance_name<HAS_VERT, HAS_BARY, CV, CHUNK>("interpolate_backward_kernel");
+  launch_as(
+      name, interpolate_backward_kernel<T, HAS_VERT, HAS_BARY, CV, CHUNK>, c.grid, 0, c.stream, c.grad_out, c.attrs, c.vi, c.index_img,
+      c.bary_img, c.V, c.C, c.vi_sN, c.H, c.W, c.tiles_x, c.attr_grad, c.bary_grad, debug_flags(), c.strip);
 }
 
 template <typename T>
@@ -1025,15 +1149,7 @@ int interpolate_backward_impl(
     const T* bary_img, int64_t N, int64_t V, int64_t C, int64_t vi_sN, int64_t H, int64_t W,
     T* attr_grad, T* bary_grad, T* ws, size_t ws_bytes, hipStream_t stream) {
   const int64_t HW = H * W;
-  // Round 6: where the rows of attr_grad are not whole 64-byte segments (C = 12, 20, 24 ...; every C that is not a multiple of
-  // four) the run sums of the wide pipeline went through the workgroup's vertex table, which costs about a quarter more than
-  // the per-run atomics aligned rows take (C = 12 0.61 ms against 0.48 for its bytes at C = 16's rate; C = 13 ... 15 0.745).
-  // With a workspace the gradient is accumulated in rows PADDED to whole segments -- every such C takes the aligned rows'
-  // path -- and compacted into attr_grad afterwards (N V C elements: 21 MB at C = 13 on the bench mesh).
-  const bool pad_possible = attr_grad && ws && !rows_are_segments<T>(C) && N * V * C > 0 &&
-      ws_bytes >= sizeof(T) * size_t(N * V * padded_row<T>(C)) && padded_row<T>(C) < (int64_t(1) << 30);
-  bool padded = false; // decided below, with the pipeline; the zero-fill goes where the atomics will
-  auto zero_grad = [&](bool to_ws) -> int {
+  auto zero_grad = [&](bool to_ws) -> int {  // the zero-fill goes where the atomics will
     if (!attr_grad || N * V * C == 0) return DRTK_OK;
     return to_ws ? fill_bytes_async(ws, 0, sizeof(T) * N * V * padded_row<T>(C), stream) : fill_bytes_async(attr_grad, 0, sizeof(T) * N * V * C, stream);
   };
@@ -1046,161 +1162,57 @@ int interpolate_backward_impl(
     return DRTK_OK;
   }
   const bool cvec = (C % 4 == 0) && (reinterpret_cast<uintptr_t>(attrs) % (4 * sizeof(T)) == 0);
+  const bool ws_usable = ws && N * V * C > 0 && ws_bytes >= sizeof(T) * size_t(N * V * padded_row<T>(C)) && padded_row<T>(C) < (int64_t(1) << 30);
+  const BackwardPlan p = plan_backward<T>(
+      C, HW, attr_grad != nullptr, bary_grad != nullptr, cvec, ws_usable, DRTK_DBG(debug_flags(), 128), DRTK_DBG(debug_flags(), 4096));
+  if (zero_grad(p.padded) != DRTK_OK) return DRTK_ERR_LAUNCH;
+
   const int tiles_x = static_cast<int>(ceil_div(W, kWave)), tiles_y = static_cast<int>(ceil_div(H, kTileRows));
-  const dim3 grid(static_cast<unsigned>(int64_t(tiles_x) * tiles_y), static_cast<unsigned>(N));
-  const dim3 block(kBlock);
-  const int strip = xcd_strip(int64_t(tiles_x) * (16 / kTileRows));
-#define LAUNCH(HV, HB, CV, CH)                                                                  \
-  DRTK_LAUNCH(                                                                           \
-      (interpolate_backward_kernel<T, HV, HB, CV, CH>), grid, block, 0, stream, grad_out, attrs, \
-      vi, index_img, bary_img, V, (int)C, vi_sN, (int)H, (int)W, tiles_x, attr_grad, bary_grad,  \
-      debug_flags(), strip)
-  // The register-scan kernel (interpolate_backward_small_kernel: lane = pixel, the 3 C products of a pixel in registers, a
-  // segmented DPP scan, a wave-private vertex table) beats the wide pipeline while 3 C values per lane are few: the wide
-  // pipeline's phase 2 runs one (corner, channel) pair per lane, so a row of 8 channels keeps 24 of 64 lanes busy and costs
-  // what a row of 16 does.  Round 5, 8 x 2048^2, both gradients, ms (register scan / wide): C = 5 0.33 / 0.54, 6 0.38 / 0.59,
-  // 7 0.44 / 0.60, 8 0.50 / 0.55, 9 0.55 / 0.67, 10 0.58 / 0.67, 11 0.67 / 0.68, 12 0.69 / 0.64; double: 6 0.61 / 0.82,
-  // 7 0.65 / 0.82, 8 0.80 / 0.80 (attributes only 0.60 / 0.46), 9 0.88 / 1.11.  The bary gradient alone (no scatter): register
-  // scan up to 12 (C = 11: 0.32 against the generic kernel's 0.46).
-#ifndef DRTK_INTERP_SMALL_MAXC_F32
-#define DRTK_INTERP_SMALL_MAXC_F32 10
-#endif
-#ifndef DRTK_INTERP_SMALL_MAXC_F64
-#define DRTK_INTERP_SMALL_MAXC_F64 7
-#endif
-#ifndef DRTK_INTERP_SMALL_INST
-#define DRTK_INTERP_SMALL_INST 12
-#endif
-  constexpr int kSmallMaxC = sizeof(T) == 4 ? DRTK_INTERP_SMALL_MAXC_F32 : DRTK_INTERP_SMALL_MAXC_F64;
-  static_assert(kSmallMaxC <= DRTK_INTERP_SMALL_INST && DRTK_INTERP_SMALL_INST <= 12, "instantiated channel counts");
-  const bool small_c = C <= kSmallMaxC || (!attr_grad && C <= DRTK_INTERP_SMALL_INST) ||
-      (sizeof(T) == 8 && C % 4 != 0 && C <= 11 && C <= DRTK_INTERP_SMALL_INST); // (double, rows not 32-byte aligned: 9 measured, 10 / 11 by the trend)
-  // wide path: the vertex gradient (+ bary gradient) for any C >= 5, float and double (round 5; round 4: C % 4 == 0,
-  // C >= 8, float only -- every other shape took the generic kernel, a chain of dependent waits per row)
-  const bool wide = attr_grad && !small_c && HW * int64_t(sizeof(T)) < (int64_t(1) << 32) && !DRTK_DBG(debug_flags(), 128);
-#ifndef DRTK_INTERP_PAD
-#define DRTK_INTERP_PAD 1
-#endif
-  // ... measured (profiles/r06/interp_bwd_by_C*.json, same box, padded / table route, ms): with both gradients C = 11 0.616 / 0.665,
-  // 12 0.554 / 0.617, 13 0.693 / 0.726, 15 0.702 / 0.735 -- but attributes only 0.497 / 0.468 at C = 11 (the lighter kernel hides
-  // the table better than the atomics), and with more than one chunk the tail chunk's few channels are a request of their own
-  // per run and corner where the table merges a vertex's chunks: C = 17 1.093 / 1.023, 20 1.071 / 0.860 (attributes only 1.039 /
-  // 0.668).  So: one chunk, both gradients, float.
-  padded = wide && pad_possible && DRTK_INTERP_PAD && bary_grad && sizeof(T) == 4 && C <= 16;
-  if (zero_grad(padded) != DRTK_OK) return DRTK_ERR_LAUNCH;
-  T* const grad_dst = padded ? ws : attr_grad;
-  const int CG = static_cast<int>(padded ? padded_row<T>(C) : C);
-  // (the bary gradient alone stays with the generic kernel: no scatter, covered pixels only -- 0.95 of the HBM peak on
-  // SURVEY 8d's bytes at the bench coverage; a forward-shaped streaming kernel with four pixels per lane, which cannot
-  // skip the background of a partly covered quad, was measured slower: 0.55 vs 0.40 ms at C = 16)
-  if (wide) {
-    // the workgroup's vertex table: as many slots as fit DRTK_INTERP_TABLE_BYTES of LDS (the staging rows take 27 KB; 4
-    // workgroups per CU leave 40 KB each), at most 128, at least 16 -- else per-run atomics as before
-#ifndef DRTK_INTERP_TABLE_BYTES
-#define DRTK_INTERP_TABLE_BYTES 12800
-#endif
-    // -- and only where the rows of attr_grad are not made of whole 64-byte segments (C = 12, 20, 24, 28, ..., every C that
-    // is not a multiple of four): there the per-run atomics are several times slower (8 x 2048^2, both gradients: C = 12
-    // 0.92 -> 0.65 ms, C = 24 1.30 -> 1.04 with the table), while on aligned rows (C = 8, 16, 32, 64) the table's lookups
-    // and barriers cost more than the fire-and-forget atomics they replace (C = 16: 0.63 -> 0.70 ms)
-    int log2_slots = 7;
-    while (log2_slots > 0 && (sizeof(TableAcc) * C + 4) * (size_t(1) << log2_slots) > DRTK_INTERP_TABLE_BYTES) --log2_slots;
-    const bool rows_aligned = padded || rows_are_segments<T>(C);
-#ifdef DRTK_INTERP_NO_TABLE
-    const bool table = false;
-#else
-    const bool table = log2_slots >= 4 && !rows_aligned && !DRTK_DBG(debug_flags(), 4096);
-#endif
-    const size_t lds = table ? (sizeof(TableAcc) * C + 4) * (size_t(1) << log2_slots) : 0;
-    // chunks of 16 channels (float; 12 for the element-aligned 11 ... 12, below), 8 for double.  Float chunks of 8 are what
-    // C <= 8 would take -- but the register-scan kernel serves every float C <= DRTK_INTERP_SMALL_MAXC_F32 = 10 since round 5,
-    // so they are instantiated only where a build makes them reachable (a lower DRTK_INTERP_SMALL_MAXC_F32, or
-    // DRTK_INTERP_CH8_ANYC for the unaligned 9 ... 15): the default library carries none of them.
-    constexpr int CH = sizeof(T) == 4 ? 16 : 8;
-    constexpr bool kCh8Reachable = sizeof(T) == 4 && DRTK_INTERP_CH8 && (DRTK_INTERP_SMALL_MAXC_F32 < 8 || DRTK_INTERP_CH8_ANYC);
-    const bool ch8 = kCh8Reachable && (C <= 8 || (DRTK_INTERP_CH8_ANYC && !cvec && C < 16));
-    // 9 <= C <= 12 on element-aligned rows: ONE chunk of 12 (the 16-channel chunk's registers put the kernel at 3 waves per
-    // SIMD there: 0.81 against 0.63 ms at C = 12, aligned vs not, same loads)
-    const bool ch12 = sizeof(T) == 4 && DRTK_INTERP_CH12 && !cvec && C > 8 && C <= DRTK_INTERP_CH12_MAXC && bary_grad;
-#define WIDE(HB, TB, AC)                                                                                                   \
-  do {                                                                                                                     \
-    bool launched8_ = false;                                                                                               \
-    if constexpr (kCh8Reachable) {                                                                                         \
-      if (ch8) {                                                                                                           \
-        DRTK_LAUNCH(                                                                                                       \
-            (interpolate_backward_wide_kernel<T, HB, TB, 8, AC>), grid, block, lds, stream, grad_out, attrs, vi, index_img, \
-            bary_img, V, (int)C, vi_sN, (int)H, (int)W, tiles_x, grad_dst, bary_grad, debug_flags(), strip, log2_slots, CG); \
-        launched8_ = true;                                                                                                 \
-      }                                                                                                                    \
-    }                                                                                                                      \
-    if (launched8_) break;                                                                                                 \
-    if (ch12 && AC && HB)                                                                                                  \
-      DRTK_LAUNCH(                                                                                                         \
-          (interpolate_backward_wide_kernel<T, HB, TB, (sizeof(T) == 4 && AC && HB ? 12 : CH), AC>), grid, block, lds, stream, grad_out, attrs, vi, index_img, \
-          bary_img, V, (int)C, vi_sN, (int)H, (int)W, tiles_x, grad_dst, bary_grad, debug_flags(), strip, log2_slots, CG);   \
-    else                                                                                                                   \
-      DRTK_LAUNCH(                                                                                                         \
-          (interpolate_backward_wide_kernel<T, HB, TB, CH, AC>), grid, block, lds, stream, grad_out, attrs, vi, index_img, \
-          bary_img, V, (int)C, vi_sN, (int)H, (int)W, tiles_x, grad_dst, bary_grad, debug_flags(), strip, log2_slots, CG);   \
-  } while (0)
-#define WIDE_T(HB, AC) \
-  if (table) WIDE(HB, true, AC); else WIDE(HB, false, AC)
-    if (bary_grad) {
-      if (cvec) { WIDE_T(true, false); } else { WIDE_T(true, true); }
-    } else {
-      if (cvec) { WIDE_T(false, false); } else { WIDE_T(false, true); }
+  const BackwardCall<T> c{
+      grad_out, attrs, vi, index_img, bary_img, V, (int)C, vi_sN, (int)H, (int)W, tiles_x, attr_grad, bary_grad,
+      xcd_strip(int64_t(tiles_x) * (16 / kTileRows)), dim3(static_cast<unsigned>(int64_t(tiles_x) * tiles_y), static_cast<unsigned>(N)), stream};
+  const bool a = attr_grad != nullptr, b = bary_grad != nullptr, v4 = p.cv == 4, c4 = p.generic_chunk == 4;
+  switch (p.route) {
+    case BackwardRoute::kScan:
+      if (a && b) launch_scan_channels<T, true, true>(c);
+      else if (a) launch_scan_channels<T, true, false>(c);
+      else launch_scan_channels<T, false, true>(c);
+      break;
+    case BackwardRoute::kWide: {  // ANYC = !cvec
+      T* const grad_dst = p.padded ? ws : attr_grad;
+      if (b && cvec) launch_wide_chunk<T, true, false>(c, p, grad_dst);
+      else if (b) launch_wide_chunk<T, true, true>(c, p, grad_dst);
+      else if (cvec) launch_wide_chunk<T, false, false>(c, p, grad_dst);
+      else launch_wide_chunk<T, false, true>(c, p, grad_dst);
+      break;
     }
-#undef WIDE_T
-#undef WIDE
-  } else if (small_c && !DRTK_DBG(debug_flags(), 128)) {
-#define SMALL(HV, HB, CN)                                                                                                   \
-  DRTK_LAUNCH(                                                                                                              \
-      (interpolate_backward_small_kernel<T, HV, HB, CN>), grid, block, 0, stream, grad_out, attrs, vi, index_img, bary_img, \
-      V, vi_sN, (int)H, (int)W, tiles_x, attr_grad, bary_grad, strip)
-#define SMALL_CASE(HV, HB, K) \
-  case K:                     \
-    if constexpr (K <= DRTK_INTERP_SMALL_INST) SMALL(HV, HB, (K <= DRTK_INTERP_SMALL_INST ? K : 1)); \
-    break;
-#define SMALL_C(HV, HB)          \
-  switch (C) {                   \
-    SMALL_CASE(HV, HB, 1) SMALL_CASE(HV, HB, 2) SMALL_CASE(HV, HB, 3) SMALL_CASE(HV, HB, 4) SMALL_CASE(HV, HB, 5) SMALL_CASE(HV, HB, 6) \
-    SMALL_CASE(HV, HB, 7) SMALL_CASE(HV, HB, 8) SMALL_CASE(HV, HB, 9) SMALL_CASE(HV, HB, 10) SMALL_CASE(HV, HB, 11) SMALL_CASE(HV, HB, 12) \
-    default: break;              \
+    case BackwardRoute::kGeneric:
+      if (a && b && c4) { if (v4) launch_generic<T, true, true, 4, 4>(c); else launch_generic<T, true, true, 1, 4>(c); }
+      else if (a && b) { if (v4) launch_generic<T, true, true, 4, 16>(c); else launch_generic<T, true, true, 1, 16>(c); }
+      else if (a) { if (c4) launch_generic<T, true, false, 1, 4>(c); else launch_generic<T, true, false, 1, 16>(c); }
+      else { if (v4) launch_generic<T, false, true, 4, 16>(c); else launch_generic<T, false, true, 1, 16>(c); }
+      break;
   }
-    if (attr_grad && bary_grad) {
-      SMALL_C(true, true)
-    } else if (attr_grad) {
-      SMALL_C(true, false)
-    } else {
-      SMALL_C(false, true)
-    }
-#undef SMALL_C
-#undef SMALL_CASE
-#undef SMALL
-  } else if (attr_grad && bary_grad) { // (the generic kernel: the profiling build's flag 128, shapes beyond the pipelines)
-    if (C <= 4) {
-      if (cvec) LAUNCH(true, true, 4, 4); else LAUNCH(true, true, 1, 4);
-    } else {
-      if (cvec) LAUNCH(true, true, 4, 16); else LAUNCH(true, true, 1, 16);
-    }
-  } else if (attr_grad) {
-    if (C <= 4) LAUNCH(true, false, 1, 4); else LAUNCH(true, false, 1, 16);
-  } else {
-    if (cvec) LAUNCH(false, true, 4, 16); else LAUNCH(false, true, 1, 16);
-  }
-#undef LAUNCH
   DRTK_RETURN_IF_LAUNCH_FAILED();
-  if (padded) {
+  if (p.padded) {
     const int64_t count = N * V * C;
-    DRTK_LAUNCH((compact_rows_kernel<T>), dim3(static_cast<unsigned>(ceil_div(count, kBlock))), dim3(kBlock), 0, stream, ws, attr_grad, count, (int)C, CG);
+    DRTK_LAUNCH((compact_rows_kernel<T>), dim3(static_cast<unsigned>(ceil_div(count, kBlock))), dim3(kBlock), 0, stream, ws, attr_grad, count, (int)C, p.CG);
     DRTK_RETURN_IF_LAUNCH_FAILED();
   }
   return DRTK_OK;
 }
 
+// ---- argument checks shared by the entry points ------------------------------------------------------------------------------------
 bool bad_common(int64_t N, int64_t V, int64_t C, int64_t F, int64_t vi_sN, int64_t H, int64_t W) {
   return N < 0 || V < 0 || C < 0 || F < 0 || H < 0 || W < 0 || C >= (1 << 20) ||
       (vi_sN != 0 && vi_sN != F * 3) || H * W >= (int64_t(1) << 31);
+}
+// ... after the sizes, in this order: the per-pixel pointers (pixel_ptrs: the caller's are all there), the per-vertex ones, and
+// the dtype last
+bool bad_inputs(drtk_dtype_t dtype, const void* attrs, const int32_t* vi, bool pixel_ptrs, int64_t N, int64_t V, int64_t C, int64_t F, int64_t H, int64_t W) {
+  if (N * H * W * C > 0 && !pixel_ptrs) return true;
+  if ((N * V * C > 0 && !attrs) || (F > 0 && !vi)) return true;
+  return dtype != DRTK_F32 && dtype != DRTK_F64;
 }
 
 } // namespace
@@ -1213,22 +1225,15 @@ static int interpolate_entry(
     const void* bary_img, int64_t N, int64_t V, int64_t C, int64_t F, int64_t vi_sN, int64_t H,
     int64_t W, void* out, int zero_background, drtk_stream_t stream) {
   if (bad_common(N, V, C, F, vi_sN, H, W)) return DRTK_ERR_INVALID_ARGUMENT;
-  if (N * H * W * C > 0 && (!index_img || !bary_img || !out)) return DRTK_ERR_INVALID_ARGUMENT;
-  if ((N * V * C > 0 && !attrs) || (F > 0 && !vi)) return DRTK_ERR_INVALID_ARGUMENT;
-  if (dtype != DRTK_F32 && dtype != DRTK_F64) return DRTK_ERR_INVALID_ARGUMENT;
+  if (bad_inputs(dtype, attrs, vi, index_img && bary_img && out, N, V, C, F, H, W)) return DRTK_ERR_INVALID_ARGUMENT;
   const size_t es = dtype_size(dtype);
   DRTK_FOR_VIEW_SLICES(N, n0, n, interpolate_entry(
       dtype, advance(attrs, n0 * V * C, es), advance_typed(vi, n0 * vi_sN), advance_typed(index_img, n0 * H * W),
       advance(bary_img, n0 * 3 * H * W, es), n, V, C, F, vi_sN, H, W, advance(out, n0 * C * H * W, es), zero_background, stream))
   hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (dtype) {
-    case DRTK_F32:
-      return interpolate_impl<float>(static_cast<const float*>(attrs), vi, index_img, static_cast<const float*>(bary_img), N, V, C, vi_sN, H, W, static_cast<float*>(out), zero_background, s);
-    case DRTK_F64:
-      return interpolate_impl<double>(static_cast<const double*>(attrs), vi, index_img, static_cast<const double*>(bary_img), N, V, C, vi_sN, H, W, static_cast<double*>(out), zero_background, s);
-    default:
-      return DRTK_ERR_INVALID_ARGUMENT;
-  }
+  if (dtype == DRTK_F32)
+    return interpolate_impl<float>(static_cast<const float*>(attrs), vi, index_img, static_cast<const float*>(bary_img), N, V, C, vi_sN, H, W, static_cast<float*>(out), zero_background, s);
+  return interpolate_impl<double>(static_cast<const double*>(attrs), vi, index_img, static_cast<const double*>(bary_img), N, V, C, vi_sN, H, W, static_cast<double*>(out), zero_background, s);
 }
 
 extern "C" int drtk_amd_interpolate(
@@ -1245,14 +1250,13 @@ extern "C" int drtk_amd_interpolate_masked(
   return interpolate_entry(dtype, attrs, vi, index_img, bary_img, N, V, C, F, vi_sN, H, W, out, 1, stream);
 }
 
+// The workspace is the padded rows of the plan: the size is asked of the plan itself -- both gradients wanted, a workspace that
+// is usable -- and is zero wherever it does not pad (the plan's padding depends on neither the image size nor the alignment).
 extern "C" int drtk_amd_interpolate_backward_workspace_bytes(drtk_dtype_t dtype, int64_t N, int64_t V, int64_t C, size_t* bytes) {
   if (!bytes || N < 0 || V < 0 || C < 0 || (dtype != DRTK_F32 && dtype != DRTK_F64)) return DRTK_ERR_INVALID_ARGUMENT;
-  const bool f32 = dtype == DRTK_F32;
-  const bool segs = f32 ? rows_are_segments<float>(C) : rows_are_segments<double>(C);
-  const int64_t row = f32 ? padded_row<float>(C) : padded_row<double>(C);
-  // only the wide pipeline's one-chunk float shapes pad (interpolate_backward_impl: 11 <= C <= 15); anything else needs no workspace
-  const bool pads = f32 && C > DRTK_INTERP_SMALL_MAXC_F32 && C <= 16;
-  *bytes = (!segs && pads && N * V > 0) ? dtype_size(dtype) * size_t(N * V * row) : 0;
+  const BackwardPlan p = dtype == DRTK_F32 ? plan_backward<float>(C, 0, true, true, true, true, false, false)
+                                           : plan_backward<double>(C, 0, true, true, true, true, false, false);
+  *bytes = (p.padded && N * V > 0) ? dtype_size(dtype) * size_t(N * V * p.CG) : 0;
   return DRTK_OK;
 }
 
@@ -1268,9 +1272,7 @@ extern "C" int drtk_amd_interpolate_backward_ws(
     // would have had elements.
     return (N * V * C > 0 && N * H * W > 0) ? DRTK_ERR_INVALID_ARGUMENT : DRTK_OK;
   }
-  if (N * H * W * C > 0 && (!grad_out || !index_img || !bary_img)) return DRTK_ERR_INVALID_ARGUMENT;
-  if ((N * V * C > 0 && !attrs) || (F > 0 && !vi)) return DRTK_ERR_INVALID_ARGUMENT;
-  if (dtype != DRTK_F32 && dtype != DRTK_F64) return DRTK_ERR_INVALID_ARGUMENT;
+  if (bad_inputs(dtype, attrs, vi, grad_out && index_img && bary_img, N, V, C, F, H, W)) return DRTK_ERR_INVALID_ARGUMENT;
   if (workspace && reinterpret_cast<uintptr_t>(workspace) % 64 != 0) return DRTK_ERR_INVALID_ARGUMENT; // rows of whole 64-byte segments
   const size_t es = dtype_size(dtype);
   // (slices of views reuse the workspace: each call leaves nothing in it)
@@ -1279,14 +1281,9 @@ extern "C" int drtk_amd_interpolate_backward_ws(
       advance_typed(index_img, n0 * H * W), advance(bary_img, n0 * 3 * H * W, es), n, V, C, F, vi_sN, H, W,
       advance(attr_grad, n0 * V * C, es), advance(bary_grad, n0 * 3 * H * W, es), workspace, workspace_bytes, stream))
   hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (dtype) {
-    case DRTK_F32:
-      return interpolate_backward_impl<float>(static_cast<const float*>(grad_out), static_cast<const float*>(attrs), vi, index_img, static_cast<const float*>(bary_img), N, V, C, vi_sN, H, W, static_cast<float*>(attr_grad), static_cast<float*>(bary_grad), static_cast<float*>(workspace), workspace_bytes, s);
-    case DRTK_F64:
-      return interpolate_backward_impl<double>(static_cast<const double*>(grad_out), static_cast<const double*>(attrs), vi, index_img, static_cast<const double*>(bary_img), N, V, C, vi_sN, H, W, static_cast<double*>(attr_grad), static_cast<double*>(bary_grad), static_cast<double*>(workspace), workspace_bytes, s);
-    default:
-      return DRTK_ERR_INVALID_ARGUMENT;
-  }
+  if (dtype == DRTK_F32)
+    return interpolate_backward_impl<float>(static_cast<const float*>(grad_out), static_cast<const float*>(attrs), vi, index_img, static_cast<const float*>(bary_img), N, V, C, vi_sN, H, W, static_cast<float*>(attr_grad), static_cast<float*>(bary_grad), static_cast<float*>(workspace), workspace_bytes, s);
+  return interpolate_backward_impl<double>(static_cast<const double*>(grad_out), static_cast<const double*>(attrs), vi, index_img, static_cast<const double*>(bary_img), N, V, C, vi_sN, H, W, static_cast<double*>(attr_grad), static_cast<double*>(bary_grad), static_cast<double*>(workspace), workspace_bytes, s);
 }
 
 extern "C" int drtk_amd_interpolate_backward(
