@@ -207,3 +207,58 @@ def expected(name, padding):
     r["out_mag"] = apply(x.double(), f, up, down, reflect, absolute=True)
     r["grad_mag"] = apply(gout.double(), f, down, up, reflect, backward=True, absolute=True) if divisible(name) else None
     return r
+
+
+# ---- 5. every tuned family ------------------------------------------------------------------------------------------------
+# The (up, down, k) csrc/filter2d.hip instantiates with compile-time taps (F2D_TUNED; tests/test_filter2d_host.py requires
+# this table to be exactly that set).  Symmetric under exchanging up and down: the gradient call of (u, d, k) is the family
+# (d, u, k) with the `backward` flag, so running forward and gradient of every entry launches every family with both
+# settings of the flag.  Not part of CASES: those have recorded fixtures.
+FAMILIES = tuple([(1, 1, k) for k in (3, 5, 7, 9, 11, 13, 17, 25, 33, 49, 65)]
+                 + [(u, d, k) for k in (4, 6, 8, 10, 12) for u, d in ((1, 2), (2, 1))]
+                 + [(u, d, k) for k in (16, 24) for u, d in ((1, 4), (4, 1))]
+                 + [(u, d, k) for k in (32, 48) for u, d in ((1, 8), (8, 1))])
+# The forward output of every family: at least two tiles per axis at the widest (64) and the tallest (32) tile of the
+# planner, a ragged last column tile at each of its widths (72 mod 64, 32, 16 = 8) and a ragged last row tile at the
+# heights 32 and 16 (40 mod 32, 16 = 8); 2 x 3 planes.
+FAMILY_OUT = (40, 72)
+FAMILY_PLANES = (2, 3)
+TILE_WIDTHS, TILE_HEIGHTS = (64, 32, 16), (32, 16, 8, 4, 2, 1)  # f2d_plan's candidates
+
+
+def family_input(up, down):
+    """(H, W) of the input: FAMILY_OUT * down / up where that is whole (every tuned family) -- else the next multiple of
+    `down` above it (a generic configuration such as (3, 2, 12): its output is then a little larger than FAMILY_OUT)."""
+    def axis(n):
+        m = -(-n * down // up)
+        return -(-m // down) * down
+
+    return tuple(axis(n) for n in FAMILY_OUT)
+
+
+@functools.lru_cache(maxsize=None)
+def family_case(up, down, k):
+    """-> (x, f, grad_out): float32 tensors, the same from call to call (do not modify them); f is random in [-1, 1)."""
+    g = th.Generator().manual_seed(20000 + 1000 * up + 100 * down + k)
+    f = th.rand(k, generator=g) * 2 - 1
+    H, W = family_input(up, down)
+    x = th.rand(*FAMILY_PLANES, H, W, generator=g) * 2 - 1
+    grad_out = th.rand(*FAMILY_PLANES, output_size(H, k, up, down), output_size(W, k, up, down), generator=g) * 2 - 1
+    return x, f, grad_out
+
+
+@functools.lru_cache(maxsize=None)
+def family_expected(up, down, k, padding, half=False):
+    """The oracle on a family's case, computed once: out / grad in float32 and float64 and the accumulated magnitudes of
+    both, like `expected`; with `half` on the inputs rounded to float16 (what a float16 image holds)."""
+    x, f, gout = family_case(up, down, k)
+    if half:
+        x, gout = x.half().float(), gout.half().float()
+    reflect = padding == "reflection"
+    r = {}
+    for tag, dt in (("32", th.float32), ("64", th.float64)):
+        r["out" + tag] = apply(x.to(dt), f, up, down, reflect)
+        r["grad" + tag] = gradient(gout.to(dt), f, up, down, reflect, x.shape)
+    r["out_mag"] = apply(x.double(), f, up, down, reflect, absolute=True)
+    r["grad_mag"] = apply(gout.double(), f, down, up, reflect, backward=True, absolute=True)
+    return r

@@ -7,6 +7,7 @@ Python signatures, and the pinned boundary of the `drtk` drop-in package."""
 import ctypes
 import inspect
 import os
+import re
 
 import numpy as np
 import pytest
@@ -148,6 +149,52 @@ def test_oracle_refuses_what_the_operator_does_not_admit():
     with pytest.raises(ValueError, match="backward"):
         O.gradient(th.zeros(1, 1, 6, 8), th.ones(12), 1, 2, False, (1, 1, 13, 17))
     assert O.apply(th.zeros(1, 1, 13, 17), th.ones(12), 1, 2).shape == (1, 1, 6, 8)
+
+
+# ---- the tuned families ------------------------------------------------------------------------------------------------------------
+def tuned_families_of_the_source():
+    src = open(os.path.join(ROOT, "drtk_amd", "csrc", "filter2d.hip")).read()
+    bodies = re.findall(r"#define F2D_TUNED\(X\)((?:[^\n]*\\\n)*[^\n]*)\n", src)
+    assert len(bodies) == 1, bodies
+    entries = re.findall(r"\bX\(([^)]*)\)", bodies[0])
+    triples = [tuple(int(t) for t in e.split(",")) for e in entries]
+    assert all(len(t) == 3 for t in triples), entries
+    return triples
+
+
+def test_families_is_exactly_the_tuned_set_of_the_source():
+    """A family added to F2D_TUNED without an entry in FAMILIES would be compiled and never launched against the oracle
+    (tests/test_gpu_filter2d.py runs FAMILIES)."""
+    tuned = tuned_families_of_the_source()
+    assert len(tuned) >= 29 and len(set(tuned)) == len(tuned), tuned
+    assert len(set(O.FAMILIES)) == len(O.FAMILIES)
+    assert set(O.FAMILIES) == set(tuned), (sorted(set(tuned) - set(O.FAMILIES)), sorted(set(O.FAMILIES) - set(tuned)))
+    # forward and gradient of every entry launch every family with both settings of the `backward` flag
+    assert {(d, u, k) for u, d, k in O.FAMILIES} == set(O.FAMILIES)
+    # ... and every tuned family is one the kernel's static_assert admits: up == 1, or down == 1 and k a multiple of up
+    assert all(u == 1 or (d == 1 and k % u == 0) for u, d, k in O.FAMILIES)
+
+
+def test_the_family_cases_reach_every_tile_shape_and_admit_gradient_and_reflection():
+    OH, OW = O.FAMILY_OUT
+    # two tiles per axis at the widest and the tallest tile; a ragged last column tile at every tile width, a ragged last row
+    # tile at the heights 32 and 16 (the lower heights divide every multiple of 8)
+    assert OW > max(O.TILE_WIDTHS) and OH > max(O.TILE_HEIGHTS)
+    assert all(OW % w != 0 for w in O.TILE_WIDTHS)
+    assert all(OH % h != 0 for h in O.TILE_HEIGHTS[:2]) and all(OH % h == 0 for h in O.TILE_HEIGHTS[2:])
+    for up, down, k in O.FAMILIES:
+        x, f, gout = O.family_case(up, down, k)
+        assert f.shape == (k,) and x.shape[:2] == gout.shape[:2] == O.FAMILY_PLANES
+        assert tuple(gout.shape[2:]) == O.FAMILY_OUT, (up, down, k)
+        for n, o in zip(x.shape[2:], gout.shape[2:]):
+            assert n * up == o * down and n % down == 0
+            assert O.geometry(n, k, up, down)[2] == o
+            assert O.geometry(o, k, down, up, backward=True)[2] == n  # the gradient call exists
+            assert O.reflect_ok(n, k, up, down) and O.reflect_ok(o, k, down, up, backward=True), (up, down, k, n)
+    # the generic configuration the guarded driver adds (tests/guarded_added_ops.py): a gradient exists there too
+    x, f, gout = O.family_case(3, 2, 12)
+    assert tuple(x.shape[2:]) == (28, 48) and tuple(gout.shape[2:]) == (42, 72)
+    assert O.gradient(gout.double(), f, 3, 2, True, x.shape).shape == x.shape
 
 
 # ---- C ABI ---------------------------------------------------------------------------------------------------------------------

@@ -106,28 +106,66 @@ def routes():
     }
 
 
+def check_grid_point(K, C, dtype, holes, H=37, W=29, names=None, use_index=True, use_background=True):
+    """problem(K, C, dtype, holes, H=H, W=W) through the routes `names` (all of them by default): the forward bit for bit
+    the loop in the same dtype on the device, the five float64 bounds of `bounds`, exact zeros at skipped layers.  Without
+    the index or without the background (the guarded driver, tests/guarded_added_ops.py) the float64 oracle is the loop
+    without it, under the same bounds."""
+    p = problem(K, C, dtype, holes, 2, H, W)
+    args = dev(p.color, p.alpha, p.index, p.bg, p.g_img, p.g_T)
+    ref = dict(img=p.img, T=p.T, gc=p.gc, ga=p.ga, gb=p.gb)
+    if not (use_index and use_background):
+        c64, a64, b64 = f64(p.color), f64(p.alpha), (f64(p.bg) if use_background else None)
+        ri, rT = loop(c64, a64, p.index if use_index else None, b64)
+        ((ri * p.g_img.double()).sum() + (rT * p.g_T.double()).sum()).backward()
+        ref = dict(img=ri.detach(), T=rT.detach(), gc=c64.grad, ga=a64.grad, gb=None if b64 is None else b64.grad)
+        args[2], args[3] = (args[2] if use_index else None), (args[3] if use_background else None)
+    want_img, want_T = loop(*args[:4])  # the loop, same dtype, on the device
+    bound = bounds(K, C, dtype, p.M)
+    for name, route in routes().items():
+        if names is not None and name not in names:
+            continue
+        img, T, gc, ga, gb = route(*args)
+        what = f"K={K} C={C} {H}x{W} {dtype} holes={holes} index={use_index} background={use_background} {name}"
+        assert img.dtype == dtype and img.shape == want_img.shape and T.shape == want_T.shape, what
+        assert th.equal(img, want_img) and th.equal(T, want_T), f"{what}: forward differs from the loop in the same dtype"
+        got = dict(img=img, T=T, gc=gc, ga=ga, gb=gb)
+        for key, r in ref.items():
+            if r is None:
+                assert got[key] is None, (what, key)
+                continue
+            assert got[key].shape == r.shape, (what, key)
+            err = float((got[key].double().cpu() - r).abs().max())
+            print(f"{what} {key}: max |d| {err:.3e}, bound {bound[key]:.3e}")
+            assert err <= bound[key], f"{what} {key}: {err:.3e} > {bound[key]:.3e}"
+        if use_index:
+            masked = (p.index == -1).to(DEV)
+            assert not bool(ga[masked].any()) and not bool(gc[masked[:, :, None].expand_as(gc)].any()), f"{what}: gradient at a skipped layer"
+
+
 @pytest.mark.parametrize("dtype", [th.float32, th.float64], ids=["f32", "f64"])
 @pytest.mark.parametrize("C", CS)
 @pytest.mark.parametrize("K", KS)
 def test_base_grid_forward_bits_and_gradient_bounds(K, C, dtype):
     for holes in (False, True):
-        p = problem(K, C, dtype, holes)
-        args = dev(p.color, p.alpha, p.index, p.bg, p.g_img, p.g_T)
-        want_img, want_T = loop(*args[:4])  # the loop, same dtype, on the device
-        bound = bounds(K, C, dtype, p.M)
-        for name, route in routes().items():
-            img, T, gc, ga, gb = route(*args)
-            what = f"K={K} C={C} {dtype} holes={holes} {name}"
-            assert img.dtype == dtype and img.shape == want_img.shape and T.shape == want_T.shape, what
-            assert th.equal(img, want_img) and th.equal(T, want_T), f"{what}: forward differs from the loop in the same dtype"
-            got = dict(img=img, T=T, gc=gc, ga=ga, gb=gb)
-            for key, ref in dict(img=p.img, T=p.T, gc=p.gc, ga=p.ga, gb=p.gb).items():
-                assert got[key].shape == ref.shape, (what, key)
-                err = float((got[key].double().cpu() - ref).abs().max())
-                print(f"{what} {key}: max |d| {err:.3e}, bound {bound[key]:.3e}")
-                assert err <= bound[key], f"{what} {key}: {err:.3e} > {bound[key]:.3e}"
-            masked = (p.index == -1).to(DEV)
-            assert not bool(ga[masked].any()) and not bool(gc[masked[:, :, None].expand_as(gc)].any()), f"{what}: gradient at a skipped layer"
+        check_grid_point(K, C, dtype, holes)
+
+
+# H x W whose pixel count leaves every remainder mod 4 -- the tail the P-pixel loads and stores of a lane end in (P = 4, or
+# 2 where 4 K P values per lane are too many) --; 37 x 29 is also more than one workgroup at P = 4.
+TAIL_SHAPES = ((37, 29), (6, 7), (5, 7), (8, 8))
+
+
+@pytest.mark.parametrize("holes", [False, True], ids=["trailing", "holes"])
+@pytest.mark.parametrize("dtype", [th.float32, th.float64], ids=["f32", "f64"])
+@pytest.mark.parametrize("H,W", TAIL_SHAPES)
+@pytest.mark.parametrize("K", range(1, 9))
+def test_every_layer_count_and_every_pixel_tail(K, H, W, dtype, holes):
+    """Every K the library instantiates (1 ... 8: K = 4 is the last at which the backward keeps four pixels per lane, 6 and
+    7 the only ones whose `present` mask is neither full-width nor small) on every tail of the pixel vectors, C = 3, through
+    every route: the checks of test_base_grid_forward_bits_and_gradient_bounds."""
+    assert sorted(h * w % 4 for h, w in TAIL_SHAPES) == [0, 1, 2, 3] and 37 * 29 > 4 * 256
+    check_grid_point(K, 3, dtype, holes, H, W)
 
 
 def test_without_index_and_without_background():

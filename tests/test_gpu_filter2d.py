@@ -141,6 +141,64 @@ def test_tuned_and_generic_instantiations_agree(name, dtype):
             assert float((tuned.double() - generic.double()).abs().max()) <= bound, (name, padding, bwd)
 
 
+def check_family(up, down, k, dtype, padding):
+    """The forward (up, down, k) and its gradient call (down, up, k, backward) on O.family_case through the C ABI against the
+    oracle under the bounds of this file's docstring -- the oracle runs on what the image type holds (the inputs rounded to
+    float16 for a half image) --, and, where (up, down, k) is a tuned family, the tuned instantiation against the generic
+    one.  Shared with tests/guarded_added_ops.py.  -> {"out" | "grad_x": (worst error, its bound)} against the oracle."""
+    from drtk_amd import capi
+
+    x, f, gout = O.family_case(up, down, k)
+    half = dtype == th.float16
+    e = O.family_expected(up, down, k, padding, half)
+    reflect = padding == "reflection"
+    fd = f.to(DEV)
+    figures = {}
+    for what, inp, (u, d, bwd), tag in (("out", x, (up, down, False), "out"), ("grad_x", gout, (down, up, True), "grad")):
+        inp = inp.to(DEV, dtype)
+        tuned = capi.filter2d(inp, fd, u, d, reflect, bwd)
+        got = tuned.cpu()
+        ref32, ref64, mag = e[tag + "32"], e[tag + "64"], e[tag + "_mag"]
+        name = f"({up}, {down}, {k}) {padding} {str(dtype).split('.')[-1]} {what}"
+        assert got.dtype == dtype and got.shape == ref64.shape and got.shape == (gout if what == "out" else x).shape, name
+        assert bool(th.isfinite(got).all()), name
+        if dtype == th.float32:
+            bound, _ = f64_distance_bound(ref32, ref64, acc_magnitude=float(mag.max()))
+            err, own = assert_within_f64_distance(got, ref32, ref64, name, acc_magnitude=float(mag.max()))
+            print(f"{name}: |kernel - f64| = {err:.3e} (oracle f32 {own:.3e}), bound {bound:.3e}")
+        elif dtype == th.float64:
+            err, bound = float((got - ref64).abs().max()), 1e-12 * float(ref64.abs().max())
+            print(f"{name}: |kernel - ref| = {err:.3e}, bound {bound:.3e}")
+            assert err <= bound, f"{name}: {err:.3e} > {bound:.3e}"
+        else:
+            f32_bound, _ = f64_distance_bound(ref32, ref64, acc_magnitude=float(mag.max()))
+            excess = (got.double() - ref64).abs() - (2.0 ** -11 * ref64.abs() + f32_bound)
+            err, bound = float((got.double() - ref64).abs().max()), float((2.0 ** -11 * ref64.abs() + f32_bound).max())
+            print(f"{name}: worst |y - f64| - bound = {float(excess.max()):.3e} (|y - f64| = {err:.3e})")
+            assert float(excess.max()) <= 0, f"{name}: an element is {float(excess.max()):.3e} beyond its bound"
+        figures[what] = (err, bound)
+        if (u, d, k) in O.FAMILIES:
+            generic = capi.filter2d(inp, fd, u, d, reflect, bwd, force_generic=True)
+            assert tuned.shape == generic.shape and bool(th.isfinite(generic).all()), name
+            bound = k * 2.0 ** -24 * float(f.abs().sum()) * float(inp.abs().max())
+            if half:
+                bound += 2.0 ** -11 * float(generic.abs().max())  # the two roundings of the output may fall on either side
+            err = float((tuned.double() - generic.double()).abs().max())
+            assert err <= bound, f"{name}: tuned against generic {err:.3e} > {bound:.3e}"
+    return figures
+
+
+@pytest.mark.parametrize("padding", O.BOTH)
+@pytest.mark.parametrize("dtype", [th.float32, th.float64, th.float16], ids=["f32", "f64", "f16"])
+@pytest.mark.parametrize("up,down,k", O.FAMILIES)
+def test_every_tuned_family_against_the_oracle(up, down, k, dtype, padding):
+    """Every compiled (up, down, k) in every storage type with either setting of the `backward` flag (the gradient call of
+    (up, down, k) is the family (down, up, k)), under both paddings, on an output of O.FAMILY_OUT: two tiles and a ragged
+    last tile per axis at every tile shape the planner may choose (tests/test_filter2d_host.py asserts that, and that
+    FAMILIES is the tuned set of the source)."""
+    check_family(up, down, k, dtype, padding)
+
+
 def test_non_contiguous_x_and_grad_out():
     import drtk_amd
 

@@ -96,9 +96,58 @@ def test_hip_route_matches_the_reference_fixtures(name, idx_dtype):
     import drtk_amd.geometry as G
 
     d32, d64 = _load("f32"), _load("f64")
-    faces, verts = _near_degenerate(d64, name)
     G.geometry_cache_clear()
     got64 = _run_all(d64, name, th.float64, idx_dtype, DEV)
+    got32 = _run_all(d32, name, th.float32, idx_dtype, DEV)
+    _check_against_the_fixtures(name, got64, got32, d32, d64)
+
+
+def _run_all_capi(d, name, dtype, dev):
+    """What _run_all computes, composed from the four geometry entry points of the C ABI (int32 topology, the numpy
+    incidence) the way csrc/torch_ops/geometry.cpp composes them: {name: tensor on the CPU}, the same keys."""
+    from drtk_amd import capi
+
+    p = lambda k: d[f"{name}_{k}"].to(dev).clone()  # noqa: E731
+    g = lambda k: p(k).to(dtype)  # noqa: E731
+    vi = p("vi").to(th.int32)
+    v = g("v")
+    V = v.shape[1]
+    inc = capi.vertex_incidence_numpy(vi.cpu().numpy(), V)
+    to_v = lambda rows: capi.geometry_vertex_gather(rows, inc, V, per_corner=True)[0]  # noqa: E731
+    res = {}
+    f = capi.geometry_face_forward(v, vi, outputs=("normals", "areas", "edges"))
+    res.update({f"face_info_{k}": f[k] for k in ("normals", "areas", "edges")})
+    pos, uv = capi.geometry_face_backward(v, vi, grad_normals=g("g_face_info_normals"), grad_areas=g("g_face_info_areas"),
+                                          grad_edges=g("g_face_info_edges"))
+    assert uv is None
+    res["face_info_grad_v"] = to_v(pos)
+    vn, sums = capi.geometry_vertex_gather(f["normals"], inc, V, normalize=True)
+    pos, _ = capi.geometry_face_backward(v, vi, grad_vert=g("g_vert_normals"), vert_sums=sums)
+    res["vert_normals"], res["vert_normals_grad_v"] = vn, to_v(pos)
+    vnf, sums = capi.geometry_vertex_gather(g("fnorms"), inc, V, normalize=True)
+    res["vert_normals_fnorms"] = vnf
+    res["vert_normals_grad_fnorms"] = capi.geometry_face_gather(g("g_vert_normals"), vi, vert_sums=sums)
+    fv, none = capi.geometry_vertex_gather(g("attr"), inc, V)
+    assert none is None
+    res["face_attribute_to_vert"] = fv
+    res["face_attribute_to_vert_grad_attr"] = capi.geometry_face_gather(g("g_face_attribute_to_vert"), vi)
+    if f"{name}_vt" in d:
+        vti, vt = p("vti").to(th.int32), g("vt")
+        T = vt.shape[1]
+        tinc = capi.vertex_incidence_numpy(vti.cpu().numpy(), T)
+        to_vt = lambda rows: capi.geometry_vertex_gather(rows, tinc, T, per_corner=True)[0]  # noqa: E731
+        f2 = capi.geometry_face_forward(v, vi, vt, vti, outputs=("dpdt", "v012", "dpdt_u"))
+        pos, uv = capi.geometry_face_backward(v, vi, vt, vti, grad_dpdt=g("g_face_dpdt"), grad_v012=g("g_face_dpdt_v012"))
+        res["face_dpdt"], res["face_dpdt_v012"], res["face_dpdt_grad_v"], res["face_dpdt_grad_vt"] = f2["dpdt"], f2["v012"], to_v(pos), to_vt(uv)
+        vb, sums = capi.geometry_vertex_gather(f2["dpdt_u"], inc, V, normalize=True)
+        pos, uv = capi.geometry_face_backward(v, vi, vt, vti, grad_vert=g("g_vert_binormals"), vert_sums=sums)
+        res["vert_binormals"], res["vert_binormals_grad_v"], res["vert_binormals_grad_vt"] = vb, to_v(pos), to_vt(uv)
+    return {k: t.detach().cpu() for k, t in res.items()}
+
+
+def _check_against_the_fixtures(name, got64, got32, d32, d64):
+    """The bounds of test_hip_route_matches_the_reference_fixtures (its docstring), on what _run_all or _run_all_capi gave."""
+    faces, verts = _near_degenerate(d64, name)
     for k, t in got64.items():
         ref = d64[f"{name}_{k}"]
         (a, a_deg), (b, b_deg) = _split(k, t, faces, verts), _split(k, ref, faces, verts)
@@ -107,7 +156,6 @@ def test_hip_route_matches_the_reference_fixtures(name, idx_dtype):
         assert bool(th.isfinite(a_deg).all()), (name, k)
         exact = b_deg == 0
         assert th.equal(a_deg[exact], b_deg[exact]) or k not in _FACE_C, (name, k)
-    got32 = _run_all(d32, name, th.float32, idx_dtype, DEV)
     assert got32.keys() == got64.keys()
     for k, t in got32.items():
         ok = [_split(k, x, faces, verts)[0] for x in (t, d32[f"{name}_{k}"], d64[f"{name}_{k}"])]

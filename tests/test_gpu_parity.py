@@ -1419,6 +1419,23 @@ def test_no_kernel_writes_outside_its_outputs_or_workspaces(guard):
         assert f"{cases}/{cases} cases passed" in r.stdout, r.stdout[-500:]
 
 
+@pytest.mark.parametrize("guard", [1, 3])
+def test_added_operators_write_nothing_outside_their_outputs(guard):
+    """The same for the operators the fuzzers above do not call -- filter2d, composite_layers, grid_scatter, msi,
+    transform_distort, the geometry entry points, rasterize_layers: tests/guarded_added_ops.py, a fixed list of small cases
+    with ragged ends against their oracles, sentinels intact after every case, in a process of its own (the binding reads
+    DRTK_CAPI_GUARD when it is imported).  Its first case shows that a damaged sentinel is reported."""
+    import re
+    import subprocess
+
+    env = dict(os.environ, DRTK_CAPI_GUARD=str(guard), DRTK_CAPI_POISON="1")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "guarded_added_ops.py")], env=env, stdout=subprocess.PIPE,
+                       stderr=subprocess.STDOUT, text=True, timeout=1500)
+    assert r.returncode == 0, f"guarded_added_ops.py with {guard} guard element(s):\n{r.stdout[-3000:]}"
+    m = re.search(r"^(\d+)/(\d+) cases passed \(DRTK_CAPI_GUARD=(\d+)\)$", r.stdout, re.M)
+    assert m is not None and m.group(1) == m.group(2) and int(m.group(2)) > 100 and int(m.group(3)) == guard, r.stdout[-500:]
+
+
 def test_c_abi_output_and_workspace_pointers_at_odd_element_offsets():
     """A C caller sub-allocating from an arena: OUTPUT pointers that are only element-aligned (ptr % 16 = 4, 8, 12)
     give the bit-identical images and nothing is written outside them -- rasterize stores its tiles as 16-byte
