@@ -31,6 +31,7 @@ from drtk_amd.interpolate import (  # noqa: F401
     interpolation_normal_matrix,
 )
 from drtk_amd.mipmap_grid_sample import mipmap_grid_sample  # noqa: F401
+from drtk_amd.mipmap_pyramid import mipmap_pyramid  # noqa: F401
 from drtk_amd.msi import msi  # noqa: F401
 from drtk_amd.rasterize import (  # noqa: F401
     get_depth_order,
@@ -51,7 +52,7 @@ __version__ = "0.1.0"
 # HIP graph) and `set_depth_order` / `get_depth_order` (the rasterizer's depth order: the reference's source, or the
 # reference as its setup.py builds it) and `rasterize_layers` / `rasterize_layers_with_depth` (the K nearest triangles per
 # pixel) with `composite_layers` (their front-to-back compositing over a background, one kernel each way) are this package's
-# additions.  The mesh geometry of drtk.utils (face_info,
+# additions, and so is `mipmap_pyramid` (the mip chain `mipmap_grid_sample` reads, one fused pass each way).  The mesh geometry of drtk.utils (face_info,
 # vert_normals, face_attribute_to_vert, face_dpdt, vert_binormals) is exported here too, and so is `grid_scatter` (the
 # splatting counterpart of grid_sample), `msi` (the multi-sphere-image background) and the eight names of `filter2d` (fused
 # alias-free up/down-sampling and low-pass filtering); the `drtk` drop-in package does not lift these three yet --
@@ -72,6 +73,7 @@ __all__ = [
     "interpolation_matrix",
     "interpolation_normal_matrix",
     "mipmap_grid_sample",
+    "mipmap_pyramid",
     "grid_scatter",
     "msi",
     "FilterType",

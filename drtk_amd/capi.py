@@ -152,6 +152,8 @@ EXPORTS = [
     "drtk_amd_msi_backward",
     "drtk_amd_composite_layers",
     "drtk_amd_composite_layers_backward",
+    "drtk_amd_mipmap_pyramid",
+    "drtk_amd_mipmap_pyramid_backward",
     "drtk_amd_filter2d_output_size",
     "drtk_amd_filter2d",
     "drtk_amd_screen_space_uv_derivative",
@@ -731,6 +733,66 @@ def composite_layers_backward(grad_img, grad_transmittance, color, alpha=None, i
             _stream(color, stream)),
         "composite_layers_backward")
     return gc, ga, gb
+
+
+def _pyramid_views(t, shape):
+    """A level [N,C,h,w] as the C ABI takes it: contiguous views, any view stride."""
+    assert tuple(t.shape) == tuple(shape), (t.shape, shape)
+    return t if (t.shape[0] == 0 or t[0].is_contiguous()) else t.contiguous()
+
+
+@_on_tensor_device
+def mipmap_pyramid(input, levels, out=None, stream=None):
+    """The `levels` mip levels of input [N,C,H,W], finest first: element 0 is `input` itself, level l is [N,C,H >> l,W >> l]
+    -- include/drtk_amd.h.  `out`: `levels` tensors to write the levels into (entry 0 is not looked at), each with
+    contiguous views; by default they are allocated here, one by one."""
+    assert input.ndim == 4, input.shape
+    N, C, H, W = input.shape
+    planes_ok = (W <= 1 or input.stride(3) == 1) and (H <= 1 or input.stride(2) == W)
+    x = input if planes_ok else input.contiguous()
+    levels = int(levels)
+    if not 1 <= levels <= 11:
+        _check(-1, "mipmap_pyramid")
+    if out is None:
+        out = [None] + [_out(N, C, H >> l, W >> l, dtype=x.dtype, device=x.device) for l in range(1, levels)]
+    assert len(out) == levels, (len(out), levels)
+    for l in range(1, levels):
+        assert out[l].dtype == x.dtype and _pyramid_views(out[l], (N, C, H >> l, W >> l)) is out[l], l
+    ptrs = (ctypes.c_void_p * levels)(*[0 if l == 0 else out[l].data_ptr() for l in range(levels)])
+    sn = (ctypes.c_int64 * levels)(*[0 if l == 0 else (out[l].stride(0) if N > 1 else out[l][0].numel() if N else 0) for l in range(levels)])
+    _check(
+        lib().drtk_amd_mipmap_pyramid(
+            ctypes.c_int(_dt(x)), _p(x), _i(x.stride(0)), _i(x.stride(1)), _i(N), _i(C), _i(H), _i(W), ctypes.c_int(levels), ptrs, sn,
+            _stream(x, stream)),
+        "mipmap_pyramid")
+    return [input] + list(out[1:])
+
+
+@_on_tensor_device
+def mipmap_pyramid_backward(grad_levels, grad_input=None, stream=None):
+    """grad_input [N,C,H,W] of the gradients of the `len(grad_levels)` levels: tensors [N,C,H >> l,W >> l], or None where a
+    level received none (taken as zeros, never read); entry 0 or `grad_input` (a contiguous tensor to write into) says what
+    H and W are, so one of the two must be given."""
+    levels = len(grad_levels)
+    given = [g for g in grad_levels if g is not None]
+    like = grad_input if grad_input is not None else grad_levels[0]
+    assert given and like is not None, "mipmap_pyramid_backward: no gradient, or neither grad_levels[0] nor grad_input"
+    N, C, H, W = like.shape
+    if not 1 <= levels <= 11:
+        _check(-1, "mipmap_pyramid_backward")
+    gl = [None if g is None else _pyramid_views(g, (N, C, H >> l, W >> l)) for l, g in enumerate(grad_levels)]
+    assert all(g is None or g.dtype == like.dtype for g in gl)
+    if grad_input is None:
+        grad_input = _out(N, C, H, W, dtype=like.dtype, device=like.device)
+    assert grad_input.is_contiguous() and grad_input.dtype == like.dtype
+    ptrs = (ctypes.c_void_p * levels)(*[0 if g is None else g.data_ptr() for g in gl])
+    sn = (ctypes.c_int64 * levels)(*[0 if g is None else (g.stride(0) if N > 1 else g[0].numel() if N else 0) for g in gl])
+    _check(
+        lib().drtk_amd_mipmap_pyramid_backward(
+            ctypes.c_int(_dt(like)), ptrs, sn, _i(N), _i(C), _i(H), _i(W), ctypes.c_int(levels), _p(grad_input),
+            _stream(like, stream)),
+        "mipmap_pyramid_backward")
+    return grad_input
 
 
 def filter2d_output_size(size, k, up=1, down=1) -> int:

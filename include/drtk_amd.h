@@ -407,6 +407,34 @@ int drtk_amd_composite_layers_backward(
     const int64_t* grad_alpha_strides, void* grad_background, drtk_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * mipmap_pyramid -- the mip chain that mipmap_grid_sampler_2d reads, made from one texture in one pass (two launches
+ * beyond seven levels), and its backward: the sampler's per-level gradients folded back into the texture in one launch.
+ * No reference counterpart (its callers loop over avg_pool2d).  In the tensor's own type, every level from the previous
+ * level as stored, in this order of operations (avg_pool2d's chain bit for bit):
+ *   h_{l+1} = h_l / 2, w_{l+1} = w_l / 2 (floor: a trailing odd row / column is dropped);
+ *   x_{l+1}[i][j] = (((x_l[2i][2j] + x_l[2i][2j+1]) + x_l[2i+1][2j]) + x_l[2i+1][2j+1]) * 0.25.
+ *   input [N,C,H,W]: every H x W plane contiguous, element strides input_sN (view) and input_sC (channel), both >= 0 --
+ *     channel slices and a view-shared texture are read in place.  It is level 0 and is not written.
+ *   out, out_sN: `levels` entries; out[l] is level l, [N,C,H >> l,W >> l] with contiguous views out_sN[l] >= 0 elements
+ *     apart, written fully, each element once.  Entry 0 is not looked at.
+ *   1 <= levels <= min(11, 1 + floor(log2(min(H, W)))), C >= 1 (any), H * W < 2^31, any N; DRTK_F32 and DRTK_F64; tensors
+ *   need the alignment of their element only (rows move as 16-byte vectors where the address allows).  Judged first,
+ *   before any pointer: dtype, sizes, levels.  N * H * W == 0 or levels == 1: DRTK_OK, nothing is looked at or launched.
+ *   No workspace, no atomics: bitwise reproducible.  Enqueues only (no sync, no host read).
+ * Backward: with g_l = grad_levels[l], [N,C,H >> l,W >> l] with contiguous views grad_sN[l] elements apart, or NULL (taken
+ *   as zeros, never read; its stride is then not looked at):
+ *   G_{levels-1} = g_{levels-1};  G_l[i][j] = g_l[i][j] + 0.25 * G_{l+1}[i/2][j/2];  grad_input = G_0, [N,C,H,W] contiguous,
+ *   written fully, each element once.  A texel of a dropped row / column has no parent and keeps g_l alone.  One add and
+ *   one exact multiply per level: the order of the sum is unique, the result is autograd of the chain bit for bit.
+ */
+int drtk_amd_mipmap_pyramid(
+    drtk_dtype_t dtype, const void* input, int64_t input_sN, int64_t input_sC, int64_t N, int64_t C, int64_t H, int64_t W, int levels,
+    void* const* out, const int64_t* out_sN, drtk_stream_t stream);
+int drtk_amd_mipmap_pyramid_backward(
+    drtk_dtype_t dtype, const void* const* grad_levels, const int64_t* grad_sN, int64_t N, int64_t C, int64_t H, int64_t W, int levels,
+    void* grad_input, drtk_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * filter2d -- fused separable up/down-sampling FIR filters: zero-insertion by `up`, a k-tap 1-D filter f (float32,
  * whatever the image's type) along both axes, decimation by `down`, one kernel, no workspace; replaces filter2d_cuda
  * (src/filter2d/filter2d.cpp, filter2d_kernel.cu) without its limits: any (up, down, k) the rule below admits (the
