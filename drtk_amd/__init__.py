@@ -24,6 +24,7 @@ from drtk_amd.geometry import (  # noqa: F401
 )
 from drtk_amd.graph import capture_step  # noqa: F401
 from drtk_amd.grid_scatter import grid_scatter  # noqa: F401
+from drtk_amd.image_loss import photometric_loss, ssim  # noqa: F401
 from drtk_amd.interpolate import (  # noqa: F401
     interpolate,
     interpolate_masked,
@@ -52,7 +53,8 @@ __version__ = "0.1.0"
 # HIP graph) and `set_depth_order` / `get_depth_order` (the rasterizer's depth order: the reference's source, or the
 # reference as its setup.py builds it) and `rasterize_layers` / `rasterize_layers_with_depth` (the K nearest triangles per
 # pixel) with `composite_layers` (their front-to-back compositing over a background, one kernel each way) are this package's
-# additions, and so is `mipmap_pyramid` (the mip chain `mipmap_grid_sample` reads, one fused pass each way).  The mesh geometry of drtk.utils (face_info,
+# additions, and so are `mipmap_pyramid` (the mip chain `mipmap_grid_sample` reads, one fused pass each way) and the image
+# losses `ssim` / `photometric_loss` (L1 and D-SSIM under the foreground mask, one fused pass each way).  The mesh geometry of drtk.utils (face_info,
 # vert_normals, face_attribute_to_vert, face_dpdt, vert_binormals) is exported here too, and so is `grid_scatter` (the
 # splatting counterpart of grid_sample), `msi` (the multi-sphere-image background) and the eight names of `filter2d` (fused
 # alias-free up/down-sampling and low-pass filtering); the `drtk` drop-in package does not lift these three yet --
@@ -74,6 +76,8 @@ __all__ = [
     "interpolation_normal_matrix",
     "mipmap_grid_sample",
     "mipmap_pyramid",
+    "ssim",
+    "photometric_loss",
     "grid_scatter",
     "msi",
     "FilterType",

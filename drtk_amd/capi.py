@@ -154,6 +154,9 @@ EXPORTS = [
     "drtk_amd_composite_layers_backward",
     "drtk_amd_mipmap_pyramid",
     "drtk_amd_mipmap_pyramid_backward",
+    "drtk_amd_image_loss_workspace_bytes",
+    "drtk_amd_image_loss_forward",
+    "drtk_amd_image_loss_backward",
     "drtk_amd_filter2d_output_size",
     "drtk_amd_filter2d",
     "drtk_amd_screen_space_uv_derivative",
@@ -793,6 +796,87 @@ def mipmap_pyramid_backward(grad_levels, grad_input=None, stream=None):
             _stream(like, stream)),
         "mipmap_pyramid_backward")
     return grad_input
+
+
+IMAGE_LOSS_MODES = {"map": 0, "ssim": 1, "photometric": 2}
+
+
+def image_loss_workspace_bytes(N, H, W, window_size=11, valid=False) -> int:
+    out = ctypes.c_size_t(0)
+    _check(
+        lib().drtk_amd_image_loss_workspace_bytes(_i(N), _i(H), _i(W), ctypes.c_int(int(window_size)), ctypes.c_int(bool(valid)), ctypes.byref(out)),
+        "image_loss")
+    return out.value
+
+
+def _image_loss_rows(t):
+    """An image [N,C,H,W] as the C ABI takes it: rows contiguous, any view / channel / row stride."""
+    assert t.ndim == 4, t.shape
+    return t if (t.shape[3] <= 1 or t.stride(3) == 1) else t.contiguous()
+
+
+def _image_loss_weight(weight, like):
+    """(tensor or None, weight_kind, strides {sN, sH}) of a weight [N,H,W] / [N,1,H,W], bool or the images' dtype."""
+    if weight is None:
+        return None, 0, (ctypes.c_int64 * 2)(0, 0)
+    N, _, H, W = like.shape
+    w = weight[:, 0] if weight.ndim == 4 else weight
+    assert tuple(w.shape) == (N, H, W) and w.dtype in (th.bool, like.dtype), (weight.shape, weight.dtype)
+    if W > 1 and w.stride(2) != 1:
+        w = w.contiguous()
+    return w, (1 if w.dtype == th.bool else 2), (ctypes.c_int64 * 2)(w.stride(0), w.stride(1))
+
+
+def _image_loss_common(img, target, weight, window_size, sigma, data_range, valid, mode, l1_weight, ssim_weight):
+    assert img.shape == target.shape and img.dtype == target.dtype, (img.shape, target.shape, img.dtype, target.dtype)
+    x, y = _image_loss_rows(img), _image_loss_rows(target)
+    w, kind, ws = _image_loss_weight(weight, x)
+    N, C, H, W = x.shape
+    strides = [(ctypes.c_int64 * 3)(*t.stride()[:3]) for t in (x, y)]
+    head = (ctypes.c_int(_dt(x)), _p(x), strides[0], _p(y), strides[1], _p(w), ctypes.c_int(kind), ws, _i(N), _i(C), _i(H), _i(W),
+            ctypes.c_int(int(window_size)), ctypes.c_double(sigma), ctypes.c_double(data_range), ctypes.c_int(bool(valid)),
+            ctypes.c_int(IMAGE_LOSS_MODES[mode]), ctypes.c_double(l1_weight), ctypes.c_double(ssim_weight))
+    return x, (x, y, w), head
+
+
+@_on_tensor_device
+def image_loss_forward(img, target, weight=None, mode="ssim", window_size=11, sigma=1.5, data_range=1.0, valid=False, l1_weight=0.8,
+                       ssim_weight=0.2, with_maps=False, stream=None):
+    """(out, maps, scalars) of drtk_amd_image_loss_forward -- include/drtk_amd.h.  `mode`: "map" (out = S [N,C,OH,OW]),
+    "ssim" or "photometric" (out has one element).  `maps` [3,N,C,OH,OW] only `with_maps` (what the backward needs),
+    `scalars` (4 doubles) only for the two means."""
+    x, keep, head = _image_loss_common(img, target, weight, window_size, sigma, data_range, valid, mode, l1_weight, ssim_weight)
+    N, C, H, W = x.shape
+    nbytes = image_loss_workspace_bytes(N, H, W, window_size, valid)  # raises on a bad window or shape, before any allocation
+    off = (int(window_size) // 2) if valid else 0
+    OH, OW = H - 2 * off, W - 2 * off
+    out = _out(N, C, OH, OW, dtype=x.dtype, device=x.device) if mode == "map" else _out(1, dtype=x.dtype, device=x.device)
+    maps = _out(3, N, C, OH, OW, dtype=x.dtype, device=x.device) if with_maps else None
+    scalars = ws = None
+    if mode != "map":
+        scalars = _out(4, dtype=th.float64, device=x.device)
+        ws = _out(nbytes // 8, dtype=th.float64, device=x.device)
+    _check(
+        lib().drtk_amd_image_loss_forward(*head, _p(out), _p(maps), _p(scalars), _p(ws), ctypes.c_size_t(nbytes), _stream(x, stream)),
+        "image_loss_forward")
+    return (out if mode == "map" else out[0]), maps, scalars
+
+
+@_on_tensor_device
+def image_loss_backward(img, target, weight, maps, grad_out, scalars, mode="ssim", window_size=11, sigma=1.5, data_range=1.0,
+                        valid=False, l1_weight=0.8, ssim_weight=0.2, stream=None):
+    """grad_img [N,C,H,W] of drtk_amd_image_loss_backward; `grad_out` is the gradient of the map (mode "map") or of the
+    scalar, `maps` and `scalars` what image_loss_forward(..., with_maps=True) returned."""
+    x, keep, head = _image_loss_common(img, target, weight, window_size, sigma, data_range, valid, mode, l1_weight, ssim_weight)
+    image_loss_workspace_bytes(x.shape[0], x.shape[2], x.shape[3], window_size, valid)
+    grad_out = grad_out.to(x.dtype).contiguous()
+    assert maps.is_contiguous() and maps.dtype == x.dtype
+    assert grad_out.numel() == (maps[0].numel() if mode == "map" else 1), grad_out.shape
+    grad = _out(*x.shape, dtype=x.dtype, device=x.device)
+    _check(
+        lib().drtk_amd_image_loss_backward(*head, _p(maps), _p(grad_out), _p(scalars), _p(grad), _stream(x, stream)),
+        "image_loss_backward")
+    return grad
 
 
 def filter2d_output_size(size, k, up=1, down=1) -> int:

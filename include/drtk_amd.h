@@ -467,6 +467,47 @@ int drtk_amd_filter2d(
     int reflect, int backward, int force_generic, void* y, drtk_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * image_loss -- SSIM and the L1 / D-SSIM photometric loss of two images under a per-pixel weight (the foreground mask of a
+ * render), one fused pass each way.  No reference counterpart.  Evaluated in the images' type, sums of the means in double:
+ *   g[i] = exp(-(i - r)^2 / (2 sigma^2)), r = window_size / 2, normalised to sum 1 (host, double); G*z the separable blur
+ *   of a channel with g.  valid == 0 ("same"): zeros outside the image, the map domain D is the image, OH = H, OW = W;
+ *   valid != 0: only windows inside the image, D is the interior, OH = H - 2r, OW = W - 2r (H, W >= window_size).
+ *   C1 = (0.01 data_range)^2, C2 = (0.03 data_range)^2;  mu_x = G*x, mu_y = G*y, s_x = G*(x x) - mu_x^2, s_y = G*(y y) - mu_y^2,
+ *   s_xy = G*(x y) - mu_x mu_y;  A1 = 2 mu_x mu_y + C1, A2 = 2 s_xy + C2, B1 = mu_x^2 + mu_y^2 + C1, B2 = s_x + s_y + C2;
+ *   S = A1 A2 / (B1 B2), [N,C,OH,OW];  ssim = sum_D(w S) / (C sum_D w) with w cropped to D;  l1 = sum(w |x - y|) / (C sum w)
+ *   over the whole image.  A weight sum of 0 makes that mean, and its gradient, 0 (decided on the device).
+ *   mode 0: out = S (contiguous [N,C,OH,OW]; weight_kind must be 0; scalars and workspace are not looked at)
+ *   mode 1: out[0] = ssim            mode 2: out[0] = l1_weight l1 + ssim_weight (1 - ssim)
+ *   img, target [N,C,H,W]: rows contiguous, strides {sN, sC, sH} in elements, all >= 0 (channel and view slices are read
+ *     in place).  weight [N,H,W], strides {sN, sH}: weight_kind 0 none (w = 1), 1 bytes (nonzero is 1), 2 the images' type;
+ *     assumed non-negative, never validated.
+ *   maps: NULL, or [3,N,C,OH,OW] contiguous, which receives dmu, dxx, dxy below (what the backward needs); without it a
+ *     call of mode 1 / 2 writes nothing but its partial sums and scalars.
+ *   scalars: 4 doubles (ssim, l1, 1 / (C sum_D w), 1 / (C sum w), an inverse being 0 where its sum is 0), read by the backward
+ *     from device memory.  workspace: drtk_amd_image_loss_workspace_bytes, 8-byte aligned: one slot of double partial sums
+ *     per workgroup, added in a fixed order by a second, one-workgroup launch.  No atomics, no zero-fill: bitwise
+ *     reproducible.  Enqueues only (no sync, no host read, no copy: the window travels in the kernel arguments).
+ * Backward, with h the upstream gradient on D, zero outside it -- grad_out is [N,C,OH,OW] (mode 0) or ONE element g, in
+ *   which case h = g w / (C sum_D w) (times -ssim_weight in mode 2), formed from `scalars`:
+ *   dmu = 2 mu_y (A2 - A1) / (B1 B2) - 2 mu_x S (1 / B1 - 1 / B2),  dxx = -S / B2,  dxy = 2 A1 / (B1 B2)
+ *   grad_img = G*(h dmu) + 2 x G*(h dxx) + y G*(h dxy)  [+ g l1_weight w sign(x - y) / (C sum w) in mode 2, sign(0) = 0],
+ *   the blurs over the maps zero-extended to the image; [N,C,H,W] contiguous, written fully.  target and weight get none.
+ * Judged first, before any pointer: dtype (DRTK_F32, DRTK_F64), mode, weight_kind, window_size odd in 3 ... 15, sigma and
+ * data_range positive and finite, N, C, H, W >= 1, H W < 2^31, the "valid" rule, the number of tiles below 2^31.
+ */
+int drtk_amd_image_loss_workspace_bytes(int64_t N, int64_t H, int64_t W, int window_size, int valid, size_t* bytes);
+int drtk_amd_image_loss_forward(
+    drtk_dtype_t dtype, const void* img, const int64_t* img_strides, const void* target, const int64_t* target_strides,
+    const void* weight, int weight_kind, const int64_t* weight_strides, int64_t N, int64_t C, int64_t H, int64_t W, int window_size,
+    double sigma, double data_range, int valid, int mode, double l1_weight, double ssim_weight, void* out, void* maps, void* scalars,
+    void* workspace, size_t workspace_bytes, drtk_stream_t stream);
+int drtk_amd_image_loss_backward(
+    drtk_dtype_t dtype, const void* img, const int64_t* img_strides, const void* target, const int64_t* target_strides,
+    const void* weight, int weight_kind, const int64_t* weight_strides, int64_t N, int64_t C, int64_t H, int64_t W, int window_size,
+    double sigma, double data_range, int valid, int mode, double l1_weight, double ssim_weight, const void* maps, const void* grad_out,
+    const void* scalars, void* grad_img, drtk_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * screen_space_uv_derivative -- vt_dxdy_img [N,H,W,2,2] = [[du/dx, dv/dx],[du/dy, dv/dy]] per pixel, the
  * Jacobian input of mipmap_grid_sampler_2d; replaces the PyTorch composite
  * drtk/screen_space_uv_derivative.py:15-80 (face_dpdt + 2x interpolate + project_points_grad + inv_ex +
