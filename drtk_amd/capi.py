@@ -91,7 +91,9 @@ def use_depth_order(order: str) -> None:
     """The rasterizer's depth-order setting (include/drtk_amd.h: drtk_amd_set_depth_order): `"fastmath"` evaluates the
     depth sum in the order of the reference AS BUILT by its setup.py (`-O3 --fast-math`), `"strict"` (the default) in the
     order its source spells.  One setting per process and library -- the torch operators call the same library and
-    follow it; DRTK_AMD_DEPTH_ORDER=fastmath in the environment sets the initial value.  Affects later launches."""
+    follow it; DRTK_AMD_DEPTH_ORDER=fastmath in the environment sets the initial value.  Affects later launches.
+    A captured graph replays the order that was active at capture, not the one set when it is replayed.  The setting is
+    process-wide: every thread and stream that uses the library shares it."""
     assert order in DEPTH_ORDERS, order
     _check(lib().drtk_amd_set_depth_order(DEPTH_ORDERS[order]), "set_depth_order")
 

@@ -74,38 +74,6 @@ __device__ __forceinline__ void atomic_add_global(T* p, T v) {
   unsafeAtomicAdd(p, v);
 }
 
-// Wave-aggregated "+1" on counters[key] for the lanes with `on` set: lanes of a wave that hit the same
-// counter (consecutive triangles of a mesh mostly land in the same few tiles) are merged into ONE
-// atomic by their first lane.  With FETCH each lane gets its own slot (old value + rank).
-template <bool FETCH>
-__device__ __forceinline__ int wave_agg_inc(int32_t* __restrict__ counters, int key, bool on) {
-  const int lane = lane_id();
-  unsigned long long todo = __ballot(on);
-  int pos = 0;
-  while (todo) {
-    const int leader = __builtin_amdgcn_readfirstlane(__builtin_ctzll(todo));
-    const int k = __builtin_amdgcn_readlane(key, leader);
-    const bool mine = on && key == k;
-    const unsigned long long same = __ballot(mine);
-    int base = 0;
-    if (lane == leader) {
-      const int cnt = __popcll(same);
-      if (FETCH) {
-        base = atomicAdd(counters + k, cnt);
-      } else {
-        atomicAdd(counters + k, cnt);
-      }
-    }
-    if (FETCH) {
-      base = __builtin_amdgcn_readlane(base, leader);
-      if (mine) pos = base + __popcll(same & ((1ull << lane) - 1ull));
-    }
-    todo &= ~same;
-  }
-  return pos;
-}
-
-
 // Four consecutive elements as ONE non-temporal 16 / 32-byte load or store (`nt`: data this launch touches once).
 // (__builtin_nontemporal_* take clang vector types, not HIP's struct wrappers.)
 template <typename T>
@@ -179,6 +147,11 @@ int depth_order_setting();
 // zeros in its counter block and scattered bins out of bounds (GPU memory fault), while every kernel node of the
 // same graph replayed correctly.  A fill kernel is a kernel node like all the others.
 int fill_bytes_async(void* p, int value, size_t bytes, hipStream_t stream);
+
+// The wireframe mode of drtk_amd_rasterize (rasterize_lines.hip), called with checked arguments.
+int rasterize_lines_dispatch(
+    drtk_dtype_t dtype, const void* v, const int32_t* vi, int64_t N, int64_t V, int64_t F, int64_t vi_sN, int64_t H,
+    int64_t W, float* depth_img, int32_t* index_img, void* workspace, size_t workspace_bytes, hipStream_t stream);
 
 inline int64_t ceil_div(int64_t a, int64_t b) {
   return (a + b - 1) / b;

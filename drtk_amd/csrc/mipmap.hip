@@ -1788,8 +1788,10 @@ __global__ __launch_bounds__(kMipBlock, wave_backward_waves_per_simd<T>()) void 
             const GlobalPtr<const T> pc = inp + c * plane;
             if (sizeof(T) == 4 && interior && !DRTK_DBG(dbg, 2)) { // (double: 12 registers spilled with the rows in flight)
               // the sixteen texels of an interior footprint as FOUR 16-byte row loads (element-aligned), like the forward --
-              // not sixteen predicated 4-byte loads, each in its own exec-mask region with its own wait.  Same products,
-              // same order.
+              // not sixteen predicated 4-byte loads, each in its own exec-mask region with its own wait.  NOT the per-cell
+              // paths' products in their order (below; what double and the ablation build take): the weights are regrouped
+              // to (gOut yc[j]) xc[i] and the grid gradient to row dot-products, so the results agree with those paths up to
+              // float summation order, in the last bits.
               typedef T Quad4 __attribute__((ext_vector_type(4), aligned(sizeof(T))));
               Quad4 row[4];
 #pragma unroll

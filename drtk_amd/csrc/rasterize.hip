@@ -29,6 +29,7 @@
 // and launches pass 4 once per layer: layer k >= 1 is "the smallest key strictly greater than layer k - 1's key at this
 // pixel", a compile-time variant of the same kernel body (kLayerPeel) with the previous layer's keys in a second LDS tile.
 #include <algorithm>
+#include <type_traits>
 
 #include "common.hpp"
 #include "segscatter.hpp" // wave_lds_sync
@@ -77,7 +78,6 @@ struct TriSetup {
   int bb_min_x, bb_min_y, bb_max_x, bb_max_y;
   bool c0, c1, c2;    // canonical edge orientation flags (vi_a <= vi_b)
   bool tl0, tl1, tl2; // top-left classification
-  uint32_t z_lo_bits; // f32 bits of a rigorous lower bound of every depth this triangle can produce (0: none)
 };
 
 // Correctly rounded n / d for 0 <= n, d > 0 from a precomputed r = RN(1/d) (IEEE division, once per
@@ -136,30 +136,27 @@ __device__ __forceinline__ T markstein2(T n, T d, T r, T q0) {
 // theorem), which -- like operands outside the safe exponent range -- takes the IEEE division.
 // Reciprocals depend on the significand only, so drtk_amd_selftest_exact_div() checks this routine
 // EXHAUSTIVELY over all 2^23 significands.
-__device__ __forceinline__ float exact_rcp(float x) {
-  const uint32_t bits = __float_as_uint(x);
-  const float ax = __uint_as_float(bits & 0x7FFFFFFFu);
-  if ((bits & 0x7FFFFFu) != 0x7FFFFFu && ax >= 0x1p-100f && ax <= 0x1p100f) {
-    const float y = __builtin_amdgcn_rcpf(x);
-    return __builtin_fmaf(y, __builtin_fmaf(-x, y, 1.0f), y);
-  }
-  return 1.0f / x;
-}
-__device__ __forceinline__ double exact_rcp(double x) {
-  return 1.0 / x;
-}
-// exact_rcp's guard and its fast form, separately (the raster loop tests the guard once per pass for the whole wave)
+// The guard and the fast form are separate functions: the raster loop tests the guard once per pass for the whole wave.
 __device__ __forceinline__ bool fast_rcp_ok(float x) {
   const uint32_t bits = __float_as_uint(x);
   const float ax = __uint_as_float(bits & 0x7FFFFFFFu);
   return ((bits & 0x7FFFFFu) != 0x7FFFFFu) & (ax >= 0x1p-100f) & (ax <= 0x1p100f);
 }
+__device__ __forceinline__ bool fast_rcp_ok(double) {
+  return true;
+}
 __device__ __forceinline__ float fast_rcp(float x) {
   const float y = __builtin_amdgcn_rcpf(x);
   return __builtin_fmaf(y, __builtin_fmaf(-x, y, 1.0f), y);
 }
-__device__ __forceinline__ bool fast_rcp_ok(double) {
-  return true;
+__device__ __forceinline__ double fast_rcp(double x) {
+  return 1.0 / x;
+}
+__device__ __forceinline__ float exact_rcp(float x) {
+  return fast_rcp_ok(x) ? fast_rcp(x) : 1.0f / x;
+}
+__device__ __forceinline__ double exact_rcp(double x) {
+  return 1.0 / x;
 }
 // fast_rcp_ok for an argument that went through epsclamp (|x| >= 1e-8 > 2^-100, NaN replaced by eps): only the upper
 // end of the range and the all-ones significand remain to be tested
@@ -180,9 +177,6 @@ __device__ __forceinline__ float smallest_positive_if<float>(bool on) {
 template <>
 __device__ __forceinline__ double smallest_positive_if<double>(bool on) {
   return __longlong_as_double(on ? 1ll : 0ll);
-}
-__device__ __forceinline__ double fast_rcp(double x) {
-  return 1.0 / x;
 }
 
 // Hierarchical-z bound.  Exactly, depth = 1 / sum_k(b_k / z_k) with b_k >= 0, sum b_k = 1, so depth >= min z.
@@ -297,47 +291,14 @@ __device__ __forceinline__ bool tri_setup(
   s.tl0 = pos ? (v12y < T(0) || (v12y == T(0) && v12x > T(0))) : (v12y > T(0) || (v12y == T(0) && v12x < T(0)));
   s.tl1 = pos ? (v02y > T(0) || (v02y == T(0) && v02x < T(0))) : (v02y < T(0) || (v02y == T(0) && v02x > T(0)));
   s.tl2 = pos ? (v01y < T(0) || (v01y == T(0) && v01x > T(0))) : (v01y > T(0) || (v01y == T(0) && v01x < T(0)));
-  s.z_lo_bits = 0; // the bound comes from the binning pass's record (tri_pre), see tile_raster_kernel
-  return true;
-}
-
-// rasterize_kernel.cu:19-40
-template <typename T>
-__device__ __forceinline__ T edge_fn(T ax, T ay, T bx, T by, T px, T py) {
-  return (py - ay) * (bx - ax) - (px - ax) * (by - ay);
-}
-template <typename T>
-__device__ __forceinline__ T canon_edge(bool a_le_b, T ax, T ay, T bx, T by, T px, T py) {
-  return a_le_b ? edge_fn(ax, ay, bx, by, px, py) : -edge_fn(bx, by, ax, ay, px, py);
-}
-
-// Coverage + depth of one pixel centre (rasterize_kernel.cu:117-156).  Returns true and the f32
-// depth bits if the fragment is kept.
-template <typename T>
-__device__ __forceinline__ bool fragment(const TriSetup<T>& s, int x, int y, uint32_t& depth_bits) {
-  const T px = static_cast<T>(x), py = static_cast<T>(y);
-  T b0 = canon_edge(s.c0, s.p1x, s.p1y, s.p2x, s.p2y, px, py) * s.sign_denom;
-  T b1 = canon_edge(s.c1, s.p2x, s.p2y, s.p0x, s.p0y, px, py) * s.sign_denom;
-  T b2 = canon_edge(s.c2, s.p0x, s.p0y, s.p1x, s.p1y, px, py) * s.sign_denom;
-  if (!((b0 >= T(0)) && (b1 >= T(0)) && (b2 >= T(0)))) return false;
-  if ((!s.tl0 && b0 == T(0)) || (!s.tl1 && b1 == T(0)) || (!s.tl2 && b2 == T(0))) return false;
-  b0 /= s.abs_denom;
-  b1 /= s.abs_denom;
-  b2 /= s.abs_denom;
-  const T depth_inverse = s.dinv0 * b0 + s.dinv1 * b1 + s.dinv2 * b2;
-  const float depth = static_cast<float>(T(1) / epsclamp(depth_inverse));
-  depth_bits = __float_as_uint(depth);
-  return true;
+  return true; // (the depth lower bound comes from the binning pass's record, tri_pre: see tile_raster_body)
 }
 
 // The work queue is sharded: a single head word serves ~88 pops per microsecond (MI355X_MICROARCH.md, "dequeue"), and
 // the ~9000 items of the bench shape, popped by 1024 workgroups, sat on it for most of the ~0.15 ms the pass takes
 // with no triangle work at all.  Item i belongs to shard i % 8; a workgroup starts on shard blockIdx % 8 (its XCD, for
 // what that is worth) and moves on to the next one when its shard runs dry.
-#ifndef DRTK_RASTER_QUEUE_SHARDS
-#define DRTK_RASTER_QUEUE_SHARDS 8
-#endif
-constexpr int kQueueShards = DRTK_RASTER_QUEUE_SHARDS;
+constexpr int kQueueShards = 8;
 constexpr int kQueueStride = 32; // int32 words between the heads (128 B: one head per memory-side line)
 constexpr uint32_t kItemEmpty = 0x80000000u; // work item flag: nothing was binned to this tile
 
@@ -358,11 +319,9 @@ struct BinLayout {
 // 2048^2 0.428 -> 0.410 ms with 512; 8 x 250k 0.686 -> 0.577 with 1280; 2 x 1M at 4096^2 0.716 -> 0.628; 8 x 1M 2.5 ->
 // 1.9 with 2048; lower thresholds only lose: 256 0.451, 192 0.487, 128 0.577 ms on the bench shape).
 constexpr int kSplit4Min = 384, kSplit4Max = 2048;
+constexpr int kSplitSlotsPerCu = 4; // workgroup slots per CU the mean list length is taken over
 inline int split_threshold(int64_t N, int64_t F) {
-#ifndef DRTK_RASTER_SPLIT_SLOTS
-#define DRTK_RASTER_SPLIT_SLOTS 4
-#endif
-  const int64_t slots = int64_t(num_compute_units()) * DRTK_RASTER_SPLIT_SLOTS; // resident raster workgroups
+  const int64_t slots = int64_t(num_compute_units()) * kSplitSlotsPerCu;
   const int64_t t = (N * F * 13) / (20 * (slots > 0 ? slots : 1)); // 0.65 x triangles per slot
   return static_cast<int>(t < kSplit4Min ? kSplit4Min : (t > kSplit4Max ? kSplit4Max : t));
 }
@@ -413,8 +372,37 @@ inline BinLayout make_layout(int64_t N, int64_t F, int64_t H, int64_t W) {
   return L;
 }
 
-// (wave_agg_inc -- the wave-aggregated "+1" on counters[key] -- lives in common.hpp: the wireframe binner uses it too)
-// Same aggregation on a pair of 32-bit counters packed in one 64-bit word: lanes with `hi` set bump the
+// Wave-aggregated "+1" on counters[key] for the lanes with `on` set: lanes of a wave that hit the same
+// counter (consecutive triangles of a mesh mostly land in the same few tiles) are merged into ONE
+// atomic by their first lane.  With FETCH each lane gets its own slot (old value + rank).
+template <bool FETCH>
+__device__ __forceinline__ int wave_agg_inc(int32_t* __restrict__ counters, int key, bool on) {
+  const int lane = lane_id();
+  unsigned long long todo = __ballot(on);
+  int pos = 0;
+  while (todo) {
+    const int leader = __builtin_amdgcn_readfirstlane(__builtin_ctzll(todo));
+    const int k = __builtin_amdgcn_readlane(key, leader);
+    const bool mine = on && key == k;
+    const unsigned long long same = __ballot(mine);
+    int base = 0;
+    if (lane == leader) {
+      const int cnt = __popcll(same);
+      if (FETCH) {
+        base = atomicAdd(counters + k, cnt);
+      } else {
+        atomicAdd(counters + k, cnt);
+      }
+    }
+    if (FETCH) {
+      base = __builtin_amdgcn_readlane(base, leader);
+      if (mine) pos = base + __popcll(same & ((1ull << lane) - 1ull));
+    }
+    todo &= ~same;
+  }
+  return pos;
+}
+// The same aggregation on a pair of 32-bit counters packed in one 64-bit word: lanes with `hi` set bump the
 // high word, the others (or, with BOTH, every lane) the low word -- one atomic per distinct key and wave.
 //   count pass (BOTH):  low += lanes, high += lanes with hi        -> {entries, positive entries}
 //   fill pass (!BOTH):  low += lanes without hi, high += lanes with hi; returns this lane's slot in its
@@ -801,9 +789,6 @@ __device__ __forceinline__ TriRow<T> make_row_state(bool valid, const TriSetup<T
   return o;
 }
 
-template <typename T>
-using TriOwn = TriRow<T>;
-
 // One step: every row shades the triangle `u` it was handed.  Coverage, depth and the packed atomicMin are the
 // reference's (rasterize_kernel.cu:117-161), evaluated per lane = per pixel.
 // STRIDE = lanes that share the triangle: 16 (one DPP row per triangle, `lane16_half` = lane % 16 + 1/2) or the whole
@@ -923,7 +908,7 @@ __device__ __forceinline__ void shade_rows(
 // Rasterize the triangles held one per lane (own-lane state `o`): `nsteps` steps, step k = lane k of every row.
 template <typename T, int TILE_SHIFT, bool EARLY_Z, bool FM, bool PEEL>
 __device__ __forceinline__ void raster_rows(
-    const TriOwn<T>& o, int nsteps, int x0, int y0, unsigned long long* __restrict__ zbuf,
+    const TriRow<T>& o, int nsteps, int x0, int y0, unsigned long long* __restrict__ zbuf,
     const unsigned long long* __restrict__ zthr, int dbg) {
   const float x0f = static_cast<float>(x0), y0f = static_cast<float>(y0);
   const float lane16_half = static_cast<float>(lane_id() & 15) + 0.5f;
@@ -944,23 +929,17 @@ __device__ __forceinline__ void raster_rows(
 // 8 waves per workgroup share one 32 KiB tile.  Registers: the lane's own triangle (19) + the row's triangle (19) + the
 // pixel loop; bounded to 80 VGPRs = 3 workgroups = 24 waves per CU, WITHOUT spills (the build fails on one: item-level
 // constants that the compiler hoists out of the item loop are rematerialised behind `asm volatile("" : "+v")`).
-#ifndef DRTK_RASTER_WAVES_PER_SIMD
-#define DRTK_RASTER_WAVES_PER_SIMD 6
-#endif
-#ifndef DRTK_RASTER_BLOCK
-#define DRTK_RASTER_BLOCK 512 // 256 (4 waves per item, 4 items per CU by LDS; DRTK_RASTER_BLOCKS_PER_CU=4): 0.305 / 0.375 ms against
-#endif                        // 0.305 / 0.36 at 100k / 250k triangles -- a wave-group holds ~3.4 triangles either way
-constexpr int kRasterBlock = DRTK_RASTER_BLOCK;
+constexpr int kRasterBlock = 512; // (workgroups of 256 threads: profiles/NOTES.md R14)
 constexpr int kRasterWaves = kRasterBlock / kWave;
 // What a raster kernel instantiation is for.  kPlain: `rasterize` ([N,H,W] images).  The two others serve rasterize_layers
 // ([N,K,H,W] images): kLayerFirst draws layer 0 -- the plain kernel with the layered image stride, nothing else -- and
 // kLayerPeel a layer k >= 1, with the previous layer's keys as a per-pixel threshold in a second LDS tile.
 constexpr int kPlain = 0, kLayerFirst = 1, kLayerPeel = 2;
 template <typename T, int MODE = kPlain>
-constexpr int raster_waves_per_simd() { // double: twice the registers per value (134 VGPRs) -> ONE workgroup (2 waves per
-  // SIMD) per CU; bounded to 128 for two it spills.  kLayerPeel, float: the second 32 KiB tile leaves room for TWO
-  // workgroups per CU by LDS (2 x 80 KB of 160 KiB), hence 4 waves per SIMD
-  return sizeof(T) == 4 ? (MODE == kLayerPeel ? (DRTK_RASTER_WAVES_PER_SIMD < 4 ? DRTK_RASTER_WAVES_PER_SIMD : 4) : DRTK_RASTER_WAVES_PER_SIMD) : 2;
+constexpr int raster_waves_per_simd() { // float: 6 (three workgroups per CU, see above).  kLayerPeel, float: the second
+  // 32 KiB tile leaves room for TWO workgroups per CU by LDS (2 x 80 KB of 160 KiB), hence 4.  double: twice the registers
+  // per value (134 VGPRs) -> ONE workgroup (2 waves per SIMD) per CU; bounded to 128 for two it spills
+  return sizeof(T) == 4 ? (MODE == kLayerPeel ? 4 : 6) : 2;
 }
 constexpr int kIdRing = 128; // accepted triangle ids waiting for set-up, per wave (power of two, >= 2 * kWave - 1)
 // Cooperative pass.  A 16-lane row walks its triangle's clipped bbox 16 pixels a pass, whatever the size: a triangle that
@@ -970,20 +949,12 @@ constexpr int kIdRing = 128; // accepted triangle ids waiting for set-up, per wa
 // triangle whose clipped bbox has at least kCoopMin pixels is therefore not queued in the wave's ring but in a list of
 // the workgroup, and after the rounds ALL waves shade it together, 512 pixels a pass, its row state -- set up once, by
 // one lane -- read from LDS.  Same fragments, same packed minimum: the image cannot change.
-#ifndef DRTK_RASTER_COOP_MIN
-#define DRTK_RASTER_COOP_MIN 256
-#endif
-#ifndef DRTK_RASTER_COOP_MIN_DENSE
-#define DRTK_RASTER_COOP_MIN_DENSE 1024
-#endif
-#ifndef DRTK_RASTER_COOP_DENSE
-#define DRTK_RASTER_COOP_DENSE 64
-#endif
+constexpr int kCoopMin = 256;
 // ... where the rows would idle, that is: in a tile whose list is long (kCoopDense entries, both groups) the ordinary
 // path already keeps all 32 rows of the workgroup busy, and moving its larger triangles (the 600-pixel bounding boxes
 // at the centre of the benchmark's sphere) to the cooperative pass only adds the pass's own costs (measured: +12 % on
 // the bench scene with one threshold of 512 for every tile) -- there the threshold is kCoopMinDense.
-constexpr int kCoopMin = DRTK_RASTER_COOP_MIN, kCoopMinDense = DRTK_RASTER_COOP_MIN_DENSE, kCoopDense = DRTK_RASTER_COOP_DENSE;
+constexpr int kCoopMinDense = 1024, kCoopDense = 64;
 constexpr int kCoopBatch = 64; // triangles set up together, one per lane of the waves' first lanes, and parked in LDS
 constexpr int kCoopMax = 256; // entries per item and phase; what does not fit takes the ordinary path
 
@@ -1019,9 +990,9 @@ __device__ __forceinline__ void tile_raster_body(
   __shared__ int s_ncoop;
   constexpr int kTriWords = sizeof(TriRow<T>) / 4;
   static_assert(sizeof(TriRow<T>) % 4 == 0, "TriRow is parked in LDS word by word");
-  __shared__ uint32_t s_tri[kCoopMin > 0 ? kCoopBatch * kTriWords : 1];
-  // the batch's set-up deals kCoopBatch / kRasterWaves entries to the first lanes of every wave (any other
-  // DRTK_RASTER_BLOCK would leave entries of s_tri unset), and the launcher's resident-workgroup count assumes
+  __shared__ uint32_t s_tri[kCoopBatch * kTriWords];
+  // the batch's set-up deals kCoopBatch / kRasterWaves entries to the first lanes of every wave (a workgroup size that
+  // does not divide the batch would leave entries of s_tri unset), and raster_resident_blocks assumes that
   // raster_waves_per_simd / 2 workgroups per CU also fit by LDS (160 KiB per CU)
   static_assert(kCoopBatch % kRasterWaves == 0 && kCoopBatch / kRasterWaves <= kWave, "cooperative batch set-up needs kRasterWaves | kCoopBatch");
   static_assert(
@@ -1261,19 +1232,18 @@ __device__ __forceinline__ void tile_raster_body(
               }
               big_cursor += kWave;
             }
-            if (kCoopMin > 0) { // large in this item's rectangle: to the workgroup's list (size == NPIX + 1: no record)
-              const bool coop = ok && size >= coop_min && size <= NPIX;
-              const unsigned long long mc = __ballot(coop);
-              if (mc != 0) {
-                const int leader = __builtin_ctzll(mc);
-                int base = 0;
-                if (lane == leader) base = atomicAdd(&s_ncoop, __popcll(mc));
-                base = __shfl(base, leader);
-                const int slot = base + mbcnt(mc);
-                if (coop && slot < kCoopMax) {
-                  s_coop[slot] = f;
-                  ok = false;
-                }
+            // large in this item's rectangle: to the workgroup's list (size == NPIX + 1: no record)
+            const bool coop = ok && size >= coop_min && size <= NPIX;
+            const unsigned long long mc = __ballot(coop);
+            if (mc != 0) {
+              const int leader = __builtin_ctzll(mc);
+              int base = 0;
+              if (lane == leader) base = atomicAdd(&s_ncoop, __popcll(mc));
+              base = __shfl(base, leader);
+              const int slot = base + mbcnt(mc);
+              if (coop && slot < kCoopMax) {
+                s_coop[slot] = f;
+                ok = false;
               }
             }
             const unsigned long long m = __ballot(ok);
@@ -1295,7 +1265,6 @@ __device__ __forceinline__ void tile_raster_body(
           const int e = ((lane & 15) << 2) | (lane >> 4);
           bool valid = e < cnt;
           int f;
-#ifndef DRTK_RASTER_NO_SORT
           if (cnt > 4) {
             const bool has = lane < cnt;
             const int slot = (head + lane) & (kIdRing - 1);
@@ -1314,9 +1283,7 @@ __device__ __forceinline__ void tile_raster_body(
             const int src = __shfl(static_cast<int>(p & 63u), e);
             f = __shfl(f_nat, src);
             if (!valid) f = 0;
-          } else
-#endif
-          {
+          } else { // at most one step: nothing to balance
             f = valid ? idq[(head + e) & (kIdRing - 1)] : 0;
           }
           head += cnt;
@@ -1345,7 +1312,7 @@ __device__ __forceinline__ void tile_raster_body(
               }
             }
           }
-          const TriOwn<T> own = make_row_state<T>(valid, s, f, z_lo, x0, y0, x1, y1);
+          const TriRow<T> own = make_row_state<T>(valid, s, f, z_lo, x0, y0, x1, y1);
           if (!DRTK_DBG(dbg, 1)) {
             if (phase == 0) {
               raster_rows<T, TILE_SHIFT, false, FM, PEEL>(own, (cnt + 3) >> 2, x0, y0, zbuf, zthr, dbg);
@@ -1355,51 +1322,50 @@ __device__ __forceinline__ void tile_raster_body(
           }
         }
         if (tid == 0) DRTK_PHASE(2 + 4 * phase); // wave 0's share of the group: 2 = first group, 6 = second
-        if (kCoopMin > 0) {
-          __syncthreads(); // every wave has screened its share: the list is complete
-          const int ncoop = min(s_ncoop, kCoopMax);
-          int t_here = tid;
-          asm volatile("" : "+v"(t_here)); // made here: hoisted out of the item loop, `first` holds a register for the whole kernel
-          const float x0f = static_cast<float>(x0), y0f = static_cast<float>(y0), first = static_cast<float>(t_here) + 0.5f;
-          for (int b0 = 0; b0 < ncoop; b0 += kCoopBatch) {
-            // set-up of a batch: wave w takes entries b0 + 8 w .. + 7, one per lane (every wave runs the set-up code once
-            // per batch instead of once per triangle); the row states are parked in LDS, from where every lane of the
-            // workgroup reads the triangle it is about to shade (one address per instruction: a broadcast)
-            if (b0 > 0) __syncthreads(); // the previous batch has been read
-            const int nb_here = min(kCoopBatch, ncoop - b0);
-            constexpr int kPerWave = kCoopBatch / kRasterWaves;
-            const int e = wave * kPerWave + lane;
-            if (lane < kPerWave && e < nb_here) {
-              const int f = s_coop[b0 + e];
-              const uint4 pre = pre_n[f];
-              TriSetup<T> s = {};
-              const bool valid = tri_setup<T>(v_n, vi_n + int64_t(f) * 3, H, W, s);
-              const TriRow<T> o = make_row_state<T>(valid, s, f, pre.z, x0, y0, x1, y1);
-              uint32_t w[kTriWords];
-              __builtin_memcpy(w, &o, sizeof(o));
+        // the cooperative pass over the workgroup's list
+        __syncthreads(); // every wave has screened its share: the list is complete
+        const int ncoop = min(s_ncoop, kCoopMax);
+        int t_here = tid;
+        asm volatile("" : "+v"(t_here)); // made here: hoisted out of the item loop, `first` holds a register for the whole kernel
+        const float x0f = static_cast<float>(x0), y0f = static_cast<float>(y0), first = static_cast<float>(t_here) + 0.5f;
+        for (int b0 = 0; b0 < ncoop; b0 += kCoopBatch) {
+          // set-up of a batch: wave w takes entries b0 + 8 w .. + 7, one per lane (every wave runs the set-up code once
+          // per batch instead of once per triangle); the row states are parked in LDS, from where every lane of the
+          // workgroup reads the triangle it is about to shade (one address per instruction: a broadcast)
+          if (b0 > 0) __syncthreads(); // the previous batch has been read
+          const int nb_here = min(kCoopBatch, ncoop - b0);
+          constexpr int kPerWave = kCoopBatch / kRasterWaves;
+          const int e = wave * kPerWave + lane;
+          if (lane < kPerWave && e < nb_here) {
+            const int f = s_coop[b0 + e];
+            const uint4 pre = pre_n[f];
+            TriSetup<T> s = {};
+            const bool valid = tri_setup<T>(v_n, vi_n + int64_t(f) * 3, H, W, s);
+            const TriRow<T> o = make_row_state<T>(valid, s, f, pre.z, x0, y0, x1, y1);
+            uint32_t w[kTriWords];
+            __builtin_memcpy(w, &o, sizeof(o));
 #pragma unroll
-              for (int j = 0; j < kTriWords; ++j) s_tri[e * kTriWords + j] = w[j];
-            }
-            __syncthreads();
-            for (int i = 0; i < nb_here; ++i) {
-              uint32_t w[kTriWords];
+            for (int j = 0; j < kTriWords; ++j) s_tri[e * kTriWords + j] = w[j];
+          }
+          __syncthreads();
+          for (int i = 0; i < nb_here; ++i) {
+            uint32_t w[kTriWords];
 #pragma unroll
-              for (int j = 0; j < kTriWords; ++j) w[j] = s_tri[i * kTriWords + j];
-              TriRow<T> u;
-              __builtin_memcpy(&u, w, sizeof(u));
-              if (!DRTK_DBG(dbg, 1)) {
-                if (phase == 0) {
-                  shade_rows<T, TILE_SHIFT, false, FM, PEEL, kRasterBlock>(u, first, x0f, y0f, zbuf, zthr, dbg);
-                } else {
-                  shade_rows<T, TILE_SHIFT, true, FM, PEEL, kRasterBlock>(u, first, x0f, y0f, zbuf, zthr, dbg);
-                }
+            for (int j = 0; j < kTriWords; ++j) w[j] = s_tri[i * kTriWords + j];
+            TriRow<T> u;
+            __builtin_memcpy(&u, w, sizeof(u));
+            if (!DRTK_DBG(dbg, 1)) {
+              if (phase == 0) {
+                shade_rows<T, TILE_SHIFT, false, FM, PEEL, kRasterBlock>(u, first, x0f, y0f, zbuf, zthr, dbg);
+              } else {
+                shade_rows<T, TILE_SHIFT, true, FM, PEEL, kRasterBlock>(u, first, x0f, y0f, zbuf, zthr, dbg);
               }
             }
           }
-          if (ncoop > 0) {
-            __syncthreads(); // all reads of the list done before it is reset (the barriers below order the reset before the next pushes)
-            if (tid == 0) s_ncoop = 0;
-          }
+        }
+        if (ncoop > 0) {
+          __syncthreads(); // all reads of the list done before it is reset (the barriers below order the reset before the next pushes)
+          if (tid == 0) s_ncoop = 0;
         }
         if (phase == 1) break;
         __syncthreads();
@@ -1545,6 +1511,56 @@ __global__ __launch_bounds__(kBlock) void exact_div_selftest_kernel(
   if (local) atomicAdd(mismatches, local);
 }
 
+// Which raster kernel a launch is: the ONE statement of the rule (tests/test_gpu_rasterize_routes.py pins it).  The tile size
+// is the layout's, the depth order the library's setting when the call began, and the mode follows the layer: `rasterize`
+// (num_layers == 0) and a rasterize_layers call with ONE layer -- [N,1,H,W] is [N,H,W] -- take the plain kernel, layer 0 of
+// more takes kLayerFirst and every later layer kLayerPeel.
+struct RasterRoute {
+  int tile_shift; // 5 or 6
+  bool fm;        // DRTK_DEPTH_ORDER_FASTMATH
+  int mode;       // kPlain, kLayerFirst, kLayerPeel
+};
+inline RasterRoute raster_route(const BinLayout& L, bool fm, int num_layers, int layer) {
+  return {L.tile_shift, fm, num_layers <= 1 ? kPlain : (layer == 0 ? kLayerFirst : kLayerPeel)};
+}
+// Persistent workgroups pulling work items: as many as can be resident (raster_waves_per_simd / 2 per CU: a workgroup is
+// two waves on every SIMD), never more than there can be items.
+template <typename T, int MODE>
+unsigned raster_resident_blocks(const BinLayout& L) {
+  return static_cast<unsigned>(std::min<int64_t>(L.max_items, int64_t(num_compute_units()) * (raster_waves_per_simd<T, MODE>() / 2)));
+}
+// f(tile shift, depth order, mode) of a route as compile-time constants
+template <typename F>
+void with_route(const RasterRoute& r, F&& f) {
+  auto shift = [&](auto fm, auto mode) {
+    if (r.tile_shift == 6) f(std::integral_constant<int, 6>{}, fm, mode); else f(std::integral_constant<int, 5>{}, fm, mode);
+  };
+  auto order = [&](auto mode) {
+    if (r.fm) shift(std::true_type{}, mode); else shift(std::false_type{}, mode);
+  };
+  if (r.mode == kPlain) order(std::integral_constant<int, kPlain>{});
+  else if (r.mode == kLayerFirst) order(std::integral_constant<int, kLayerFirst>{});
+  else order(std::integral_constant<int, kLayerPeel>{});
+}
+// The one place that names a raster instantiation and launches it.  `shared`: the arguments both entry templates take, in
+// their order; the layer kernels take `num_layers` and `layer` after them.  The timing report says
+// "tile_raster_kernel<T, 6, false>" or "tile_raster_layer_kernel<T, 5, true, 2>" (common.hpp: instance_name).
+template <typename T, typename... A>
+void launch_raster(const RasterRoute& route, const BinLayout& L, hipStream_t stream, int num_layers, int layer, A... shared) {
+  with_route(route, [&](auto shift, auto fm, auto mode) {
+    constexpr int SHIFT = decltype(shift)::value, MODE = decltype(mode)::value;
+    constexpr bool FM = decltype(fm)::value;
+    const dim3 grid(raster_resident_blocks<T, MODE>(L));
+    if constexpr (MODE == kPlain) {
+      static const std::string name = instance_name<SHIFT, FM>("tile_raster_kernel");
+      launch_as(name, tile_raster_kernel<T, SHIFT, FM>, grid, kRasterBlock, 0, stream, shared...);
+    } else {
+      static const std::string name = instance_name<SHIFT, FM, MODE>("tile_raster_layer_kernel");
+      launch_as(name, tile_raster_layer_kernel<T, SHIFT, FM, MODE>, grid, kRasterBlock, 0, stream, shared..., num_layers, layer);
+    }
+  });
+}
+
 // num_layers == 0: `rasterize` ([N,H,W] images).  num_layers >= 1: rasterize_layers ([N,K,H,W] images): the bins are
 // built once, then one raster launch per layer, each on the same work list with the queue's heads rewound; layer k >= 1
 // reads layer k - 1 from the images as its threshold (stream order makes it visible).
@@ -1556,7 +1572,6 @@ int rasterize_impl(
   const BinLayout L = make_layout(N, F, H, W);
   if (workspace_bytes < L.total_bytes) return DRTK_ERR_WORKSPACE_TOO_SMALL;
   if (N * H * W == 0) return DRTK_OK;
-  if (num_layers == 1) num_layers = 0; // [N,1,H,W] is [N,H,W]: the plain kernel
   char* ws = static_cast<char*>(workspace);
   auto* tile_count = reinterpret_cast<unsigned long long*>(ws + L.off_count);
   auto* tile_cursor = reinterpret_cast<unsigned long long*>(ws + L.off_cursor);
@@ -1590,66 +1605,58 @@ int rasterize_impl(
         (int)L.tiles_per_view, tile_offset, tile_cursor, pairs);
     DRTK_RETURN_IF_LAUNCH_FAILED();
   }
-  // persistent workgroups pulling work items: as many as can be resident, never more than items
-#ifdef DRTK_RASTER_BLOCKS_PER_CU
-  const int64_t resident = int64_t(num_compute_units()) * DRTK_RASTER_BLOCKS_PER_CU;
-#else
-  const int64_t resident = int64_t(num_compute_units()) * (raster_waves_per_simd<T>() / 2);
-#endif
-  const unsigned blocks = static_cast<unsigned>(std::min<int64_t>(L.max_items, resident));
-#define DRTK_RASTER_LAUNCH(SHIFT, FM)                                                                              \
-  DRTK_LAUNCH(                                                                                                    \
-      (tile_raster_kernel<T, SHIFT, FM>), dim3(blocks), dim3(kRasterBlock), 0, stream, v, vi, (int)F, V, vi_sN,   \
-      (int)H, (int)W, L.tiles_x, (int)L.tiles_per_view, tile_offset, tile_count, view_stats, pairs, big_count,    \
-      big_list, tri_range, tri_pre, items, queue, depth_img, index_img, debug_flags())
-  const bool fm = depth_order_setting() == DRTK_DEPTH_ORDER_FASTMATH;
-  if (num_layers == 0) {
-    if (L.tile_shift == 6) {
-      if (fm) DRTK_RASTER_LAUNCH(6, true); else DRTK_RASTER_LAUNCH(6, false);
-    } else {
-      if (fm) DRTK_RASTER_LAUNCH(5, true); else DRTK_RASTER_LAUNCH(5, false);
-    }
-    DRTK_RETURN_IF_LAUNCH_FAILED();
-    return DRTK_OK;
-  }
-#undef DRTK_RASTER_LAUNCH
-  const unsigned peel_blocks =
-      static_cast<unsigned>(std::min<int64_t>(L.max_items, int64_t(num_compute_units()) * (raster_waves_per_simd<T, kLayerPeel>() / 2)));
-#define DRTK_LAYER_LAUNCH(SHIFT, FM, MODE, BLOCKS)                                                                 \
-  DRTK_LAUNCH(                                                                                                    \
-      (tile_raster_layer_kernel<T, SHIFT, FM, MODE>), dim3(BLOCKS), dim3(kRasterBlock), 0, stream, v, vi, (int)F, V, \
-      vi_sN, (int)H, (int)W, L.tiles_x, (int)L.tiles_per_view, tile_offset, tile_count, view_stats, pairs, big_count, \
-      big_list, tri_range, tri_pre, items, queue, depth_img, index_img, debug_flags(), num_layers, layer)
-  for (int layer = 0; layer < num_layers; ++layer) {
-    if (layer == 0) {
-      if (L.tile_shift == 6) {
-        if (fm) DRTK_LAYER_LAUNCH(6, true, kLayerFirst, blocks); else DRTK_LAYER_LAUNCH(6, false, kLayerFirst, blocks);
-      } else {
-        if (fm) DRTK_LAYER_LAUNCH(5, true, kLayerFirst, blocks); else DRTK_LAYER_LAUNCH(5, false, kLayerFirst, blocks);
-      }
-    } else {
-      // rewind the shards' heads (queue[1], the number of items, stays): the same work list serves every layer
+  // one raster launch per layer (`rasterize`: one launch), each on the same work list
+  const bool fm = depth_order_setting() == DRTK_DEPTH_ORDER_FASTMATH; // read once per call: every layer in one order
+  for (int layer = 0; layer < (num_layers == 0 ? 1 : num_layers); ++layer) {
+    if (layer > 0) { // rewind the shards' heads (queue[1], the number of items, stays)
       if (fill_bytes_async(queue + kQueueStride, 0, sizeof(int32_t) * kQueueStride * kQueueShards, stream) != DRTK_OK) return DRTK_ERR_LAUNCH;
-      if (L.tile_shift == 6) {
-        if (fm) DRTK_LAYER_LAUNCH(6, true, kLayerPeel, peel_blocks); else DRTK_LAYER_LAUNCH(6, false, kLayerPeel, peel_blocks);
-      } else {
-        if (fm) DRTK_LAYER_LAUNCH(5, true, kLayerPeel, peel_blocks); else DRTK_LAYER_LAUNCH(5, false, kLayerPeel, peel_blocks);
-      }
     }
+    launch_raster<T>(
+        raster_route(L, fm, num_layers, layer), L, stream, num_layers, layer, v, vi, (int)F, V, vi_sN, (int)H, (int)W, L.tiles_x,
+        (int)L.tiles_per_view, tile_offset, tile_count, view_stats, pairs, big_count, big_list, tri_range, tri_pre, items, queue,
+        depth_img, index_img, debug_flags());
     DRTK_RETURN_IF_LAUNCH_FAILED();
   }
-#undef DRTK_LAYER_LAUNCH
+  return DRTK_OK;
+}
+
+int rasterize_dispatch(
+    drtk_dtype_t dtype, const void* v, const int32_t* vi, int64_t N, int64_t V, int64_t F, int64_t vi_sN, int64_t H, int64_t W,
+    float* depth_img, int32_t* index_img, void* workspace, size_t workspace_bytes, hipStream_t s, int num_layers) {
+  if (dtype == DRTK_F32)
+    return rasterize_impl<float>(static_cast<const float*>(v), vi, N, V, F, vi_sN, H, W, depth_img, index_img, workspace, workspace_bytes, s, num_layers);
+  return rasterize_impl<double>(static_cast<const double*>(v), vi, N, V, F, vi_sN, H, W, depth_img, index_img, workspace, workspace_bytes, s, num_layers);
+}
+
+// The argument check of drtk_amd_rasterize and drtk_amd_rasterize_layers, complete before either touches the device
+// (tests/test_rasterize_args_host.py pins every status and which of two coinciding faults wins).  `planes`: images per view
+// (the K of rasterize_layers, 1 for rasterize).  DRTK_ERR_WORKSPACE_TOO_SMALL is not decided here: it comes from
+// rasterize_impl / rasterize_lines_dispatch, after all of this.
+int check_raster_args(
+    drtk_dtype_t dtype, const void* v, const int32_t* vi, int64_t N, int64_t V, int64_t F, int64_t vi_sN, int64_t H, int64_t W,
+    int64_t planes, bool wireframe, const float* depth_img, const int32_t* index_img, const void* workspace) {
+  if (N < 0 || V < 0 || F < 0 || H <= 0 || W <= 0) return DRTK_ERR_INVALID_ARGUMENT; // :464-468
+  // 64-bit counters / packed pixels updated with 64-bit atomics live in the workspace (include/drtk_amd.h, alignment)
+  if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return DRTK_ERR_INVALID_ARGUMENT;
+  if (V >= 0x10000000LL) return DRTK_ERR_TOO_MANY_VERTICES; // :459-462
+  if (dtype != DRTK_F32 && dtype != DRTK_F64) return DRTK_ERR_INVALID_ARGUMENT;
+  if (vi_sN != 0 && vi_sN != F * 3) return DRTK_ERR_INVALID_ARGUMENT;
+  // more views than one launch takes: the entry point calls itself on slices, and the limits and pointers are judged there
+  if (N > kMaxViewsPerLaunch) return DRTK_OK;
+  if (N * planes * H * W >= (int64_t(1) << 40)) return DRTK_ERR_INVALID_ARGUMENT;
+  // the bins' limits: tile coordinates in 16 bits, list entries in 31; the wireframe mode has no bins and takes no
+  // workspace here (rasterize_lines_dispatch asks for its own)
+  if (!wireframe && (H > 65535LL * 32 || W > 65535LL * 32 || N * F >= (int64_t(1) << 31) / kMaxSmallTiles)) return DRTK_ERR_INVALID_ARGUMENT;
+  if (N * H * W > 0 && (!depth_img || !index_img || (!wireframe && !workspace))) return DRTK_ERR_INVALID_ARGUMENT;
+  // Triangles need vertices: with F > 0 an empty `v` (V == 0, no storage) is rejected here on purpose -- every
+  // non-degenerate index would be read off a null base (like the reference, the kernels do not bounds-check vi).
+  if (N * F > 0 && (!v || !vi)) return DRTK_ERR_INVALID_ARGUMENT;
   return DRTK_OK;
 }
 
 } // namespace
 } // namespace drtk_amd
 
-namespace drtk_amd {
-int rasterize_lines_dispatch( // rasterize_lines.hip
-    drtk_dtype_t dtype, const void* v, const int32_t* vi, int64_t N, int64_t V, int64_t F, int64_t vi_sN, int64_t H,
-    int64_t W, float* depth_img, int32_t* index_img, void* workspace, size_t workspace_bytes, hipStream_t stream);
-}
 using namespace drtk_amd;
 
 extern "C" int drtk_amd_rasterize_workspace_bytes(
@@ -1663,42 +1670,15 @@ extern "C" int drtk_amd_rasterize(
     drtk_dtype_t dtype, const void* v, const int32_t* vi, int64_t N, int64_t V, int64_t F,
     int64_t vi_sN, int64_t H, int64_t W, int wireframe, float* depth_img, int32_t* index_img,
     void* workspace, size_t workspace_bytes, drtk_stream_t stream) {
-  if (N < 0 || V < 0 || F < 0 || H <= 0 || W <= 0) return DRTK_ERR_INVALID_ARGUMENT; // :464-468
-  // 64-bit counters / packed pixels updated with 64-bit atomics live in the workspace (include/drtk_amd.h, alignment)
-  if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return DRTK_ERR_INVALID_ARGUMENT;
-  if (V >= 0x10000000LL) return DRTK_ERR_TOO_MANY_VERTICES;                           // :459-462
-  if (dtype != DRTK_F32 && dtype != DRTK_F64) return DRTK_ERR_INVALID_ARGUMENT;
-  if (vi_sN != 0 && vi_sN != F * 3) return DRTK_ERR_INVALID_ARGUMENT;
-  // more views than one launch takes: slices, each reusing the workspace (sized for all N: enough for any slice)
+  const int st = check_raster_args(dtype, v, vi, N, V, F, vi_sN, H, W, 1, wireframe != 0, depth_img, index_img, workspace);
+  if (st != DRTK_OK) return st;
+  // slices, each reusing the workspace (sized for all N: enough for any slice)
   DRTK_FOR_VIEW_SLICES(N, n0, n, drtk_amd_rasterize(
       dtype, advance(v, n0 * V * 3, dtype_size(dtype)), advance_typed(vi, n0 * vi_sN), n, V, F, vi_sN, H, W, wireframe,
       advance_typed(depth_img, n0 * H * W), advance_typed(index_img, n0 * H * W), workspace, workspace_bytes, stream))
-  if (wireframe) {
-    if (N * H * W >= (int64_t(1) << 40)) return DRTK_ERR_INVALID_ARGUMENT;
-    if (N * H * W > 0 && (!depth_img || !index_img)) return DRTK_ERR_INVALID_ARGUMENT;
-    // Triangles need vertices: with F > 0 an empty `v` (V == 0, no storage) is rejected here on purpose -- every
-  // non-degenerate index would be read off a null base (like the reference, the kernels do not bounds-check vi).
-  if (N * F > 0 && (!v || !vi)) return DRTK_ERR_INVALID_ARGUMENT;
-    if (vi_sN != 0 && vi_sN != F * 3) return DRTK_ERR_INVALID_ARGUMENT;
-    return rasterize_lines_dispatch(dtype, v, vi, N, V, F, vi_sN, H, W, depth_img, index_img, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
-  }
-  if (H > 65535LL * 32 || W > 65535LL * 32 || N * F >= (int64_t(1) << 31) / kMaxSmallTiles ||
-      N * H * W >= (int64_t(1) << 40))
-    return DRTK_ERR_INVALID_ARGUMENT;
-  if (N * H * W > 0 && (!depth_img || !index_img || !workspace)) return DRTK_ERR_INVALID_ARGUMENT;
-  // Triangles need vertices: with F > 0 an empty `v` (V == 0, no storage) is rejected here on purpose -- every
-  // non-degenerate index would be read off a null base (like the reference, the kernels do not bounds-check vi).
-  if (N * F > 0 && (!v || !vi)) return DRTK_ERR_INVALID_ARGUMENT;
-  if (vi_sN != 0 && vi_sN != F * 3) return DRTK_ERR_INVALID_ARGUMENT;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (dtype) {
-    case DRTK_F32:
-      return rasterize_impl<float>(static_cast<const float*>(v), vi, N, V, F, vi_sN, H, W, depth_img, index_img, workspace, workspace_bytes, s);
-    case DRTK_F64:
-      return rasterize_impl<double>(static_cast<const double*>(v), vi, N, V, F, vi_sN, H, W, depth_img, index_img, workspace, workspace_bytes, s);
-    default:
-      return DRTK_ERR_INVALID_ARGUMENT;
-  }
+  if (wireframe) return rasterize_lines_dispatch(dtype, v, vi, N, V, F, vi_sN, H, W, depth_img, index_img, workspace, workspace_bytes, s);
+  return rasterize_dispatch(dtype, v, vi, N, V, F, vi_sN, H, W, depth_img, index_img, workspace, workspace_bytes, s, 0);
 }
 
 extern "C" int drtk_amd_rasterize_layers_workspace_bytes(
@@ -1713,26 +1693,13 @@ extern "C" int drtk_amd_rasterize_layers(
     int64_t vi_sN, int64_t H, int64_t W, int num_layers, float* depth_img, int32_t* index_img,
     void* workspace, size_t workspace_bytes, drtk_stream_t stream) {
   if (num_layers < 1 || num_layers > DRTK_AMD_MAX_RASTER_LAYERS) return DRTK_ERR_INVALID_ARGUMENT;
-  if (N < 0 || V < 0 || F < 0 || H <= 0 || W <= 0) return DRTK_ERR_INVALID_ARGUMENT;
-  if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return DRTK_ERR_INVALID_ARGUMENT;
-  if (V >= 0x10000000LL) return DRTK_ERR_TOO_MANY_VERTICES;
-  if (dtype != DRTK_F32 && dtype != DRTK_F64) return DRTK_ERR_INVALID_ARGUMENT;
-  if (vi_sN != 0 && vi_sN != F * 3) return DRTK_ERR_INVALID_ARGUMENT;
   const int64_t K = num_layers;
-  // more views than one launch takes: slices, each reusing the workspace (sized for all N: enough for any slice)
+  const int st = check_raster_args(dtype, v, vi, N, V, F, vi_sN, H, W, K, false, depth_img, index_img, workspace);
+  if (st != DRTK_OK) return st;
   DRTK_FOR_VIEW_SLICES(N, n0, n, drtk_amd_rasterize_layers(
       dtype, advance(v, n0 * V * 3, dtype_size(dtype)), advance_typed(vi, n0 * vi_sN), n, V, F, vi_sN, H, W, num_layers,
       advance_typed(depth_img, n0 * K * H * W), advance_typed(index_img, n0 * K * H * W), workspace, workspace_bytes, stream))
-  if (H > 65535LL * 32 || W > 65535LL * 32 || N * F >= (int64_t(1) << 31) / kMaxSmallTiles ||
-      N * K * H * W >= (int64_t(1) << 40))
-    return DRTK_ERR_INVALID_ARGUMENT;
-  if (N * H * W > 0 && (!depth_img || !index_img || !workspace)) return DRTK_ERR_INVALID_ARGUMENT;
-  // Triangles need vertices, as in drtk_amd_rasterize
-  if (N * F > 0 && (!v || !vi)) return DRTK_ERR_INVALID_ARGUMENT;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == DRTK_F32)
-    return rasterize_impl<float>(static_cast<const float*>(v), vi, N, V, F, vi_sN, H, W, depth_img, index_img, workspace, workspace_bytes, s, num_layers);
-  return rasterize_impl<double>(static_cast<const double*>(v), vi, N, V, F, vi_sN, H, W, depth_img, index_img, workspace, workspace_bytes, s, num_layers);
+  return rasterize_dispatch(dtype, v, vi, N, V, F, vi_sN, H, W, depth_img, index_img, workspace, workspace_bytes, static_cast<hipStream_t>(stream), num_layers);
 }
 
 extern "C" int drtk_amd_selftest_exact_div(

@@ -21,7 +21,11 @@ def set_depth_order(order: str) -> None:
     build of the reference computes.  `"fastmath"`: the order of the reference AS BUILT by its own setup.py:22-24
     (`-O3 --fast-math`): the last bit of ~40 % of the depths moves and with it the owner of a handful of exact near-tie
     pixels per 2048^2 view; `index_img` then equals that build's bit for bit (tests/golden/fastmath_owner_changes_*.npz).
-    `DRTK_AMD_DEPTH_ORDER=fastmath` in the environment selects it without a code change."""
+    `DRTK_AMD_DEPTH_ORDER=fastmath` in the environment selects it without a code change.
+
+    The order is read when a call is launched and is part of the kernel that call launches: a captured graph
+    (`torch.cuda.graph`, `capture_step`) replays the order that was active at capture, whatever is set afterwards.  The
+    setting is process-wide: one value shared by every thread and stream that uses the library."""
     if order not in _DEPTH_ORDERS:
         raise ValueError(f"depth order must be one of {sorted(_DEPTH_ORDERS)}, got {order!r}")
     status = ctypes.CDLL(native_library_paths()[0]).drtk_amd_set_depth_order(_DEPTH_ORDERS[order])

@@ -111,7 +111,10 @@ typedef enum {
  * drtk_amd_rasterize launches from now on.  Initial value: DRTK_DEPTH_ORDER_FASTMATH if the environment holds
  * DRTK_AMD_DEPTH_ORDER=fastmath when the setting is first read or written, else DRTK_DEPTH_ORDER_STRICT.  The torch
  * operators (torch.ops.rasterize_ext.rasterize, drtk.rasterize) call the same entry point and follow it.
- * Set it before the first rasterize call of a deployment; a change is atomic and affects later launches only. */
+ * Set it before the first rasterize call of a deployment; a change is atomic and affects later launches only.
+ * The order is part of the kernel a call launches: a captured graph (hipGraph, torch.cuda.graph) replays the order that
+ * was active when it was captured, whatever is set afterwards.  The setting is process-wide: one value shared by every
+ * thread and stream that uses the library. */
 int drtk_amd_set_depth_order(int order); /* DRTK_OK, or DRTK_ERR_INVALID_ARGUMENT for anything but the two values */
 int drtk_amd_get_depth_order(void);      /* a drtk_depth_order_t */
 int drtk_amd_rasterize_workspace_bytes(int64_t N, int64_t F, int64_t H, int64_t W, size_t* bytes);

@@ -62,12 +62,12 @@ MARGIN = 5.0      # centres: uniform over the canvas and this many pixels around
 
 # The named cases.  Sized against these constants of drtk_amd/csrc/rasterize.hip (tests/test_rasterize_layers_host.py reads
 # the numbers from the source, so a kernel change that un-targets a case shows):
-#   kMaxSmallTiles = 4 (:69)           a triangle whose bbox touches more tiles goes to the per-view list of big triangles
-#   kSplit4Min = 384 (:360)            a tile whose list is longer is split 2x2, longer than 4 x 384: 4x4 -- but
-#   max_split_log (:549)               sub-rectangles are at least 16 px, so a 32-pixel tile is split 2x2 at the most
-#   t64 >= 2048 (:380)                 N * ceil(W/64) * ceil(H/64) at or above: 64-pixel tiles, below: 32-pixel tiles
-#   DRTK_RASTER_COOP_MIN 256 (:974)    a triangle whose bbox clipped to an item has at least that many pixels is shaded
-#                                      by the whole workgroup (1024 in a tile whose list has 64 entries or more, :977-980)
+#   kMaxSmallTiles = 4 (:70)           a triangle whose bbox touches more tiles goes to the per-view list of big triangles
+#   kSplit4Min = 384 (:321)            a tile whose list is longer is split 2x2, longer than 4 x 384: 4x4 -- but
+#   max_split_log (:537)               sub-rectangles are at least 16 px, so a 32-pixel tile is split 2x2 at the most
+#   t64 >= 2048 (:339)                 N * ceil(W/64) * ceil(H/64) at or above: 64-pixel tiles, below: 32-pixel tiles
+#   kCoopMin = 256 (:952)              a triangle whose bbox clipped to an item has at least that many pixels is shaded
+#                                      by the whole workgroup (1024 in a tile whose list has 64 entries or more, :957)
 CASES = {
     "free": dict(seed=1, N=2, F=300, H=48, W=80, scale=30.0, depth="free", per_view=True),
     "ties": dict(seed=2, N=1, F=600, H=40, W=56, scale=24.0, depth="quant", big=2),
@@ -81,10 +81,10 @@ CASES = {
     "tiles64": dict(seed=8, N=2100, F=60, H=20, W=24, scale=20.0, depth="free", big=1),
     # 64-pixel tiles AND a list longer than 4 x 384 in one of them (the soup is confined to the second of eight tile
     # columns): the 4x4 split, whose lower sub-rectangles lie off the canvas.  N * F is small enough for split_threshold()
-    # (:361-368) to stay at kSplit4Min.  Three views of the batch hold a soup, in the others every vertex is (0, 0, 0) --
+    # (:323-327) to stay at kSplit4Min.  Three views of the batch hold a soup, in the others every vertex is (0, 0, 0) --
     # culled, so the oracle has nothing to do there and every layer is empty
     "heavy64": dict(seed=9, N=3, views=256, F=2000, H=20, W=449, scale=12.0, depth="free", big=2, window=(70.0, 0.0, 50.0, 20.0)),
-    # Aimed at the peel cull (:1331-1346), which drops a triangle whose depth upper bound z_hi (z_upper_bound_bits, :213-225)
+    # Aimed at the peel cull (:1298-1313), which drops a triangle whose depth upper bound z_hi (z_upper_bound_bits, :208-219)
     # is below `near`, the nearest threshold of the 8x8 blocks it touches.  Here z_hi and `near` are as close as they get:
     # every triangle lies flat at the one depth LEVEL, so from layer 1 on `near` is LEVEL in every block that is covered
     # at all, and z_hi = LEVEL / (1 - delta) + 8 ulps with delta = 40 * 5.97e-8 * ext^2 / |den| + 2e-6, smallest for the

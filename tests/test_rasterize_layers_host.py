@@ -283,7 +283,7 @@ def test_the_soups_are_sized_against_the_kernel_constants_as_the_source_states_t
     max_small = const(r"\bkMaxSmallTiles\s*=\s*(\d+)")
     split_min = const(r"\bkSplit4Min\s*=\s*(\d+)")
     t64_min = const(r"\bt64\s*>=\s*(\d+)")
-    coop_min = const(r"#define\s+DRTK_RASTER_COOP_MIN\s+(\d+)")
+    coop_min = const(r"\bkCoopMin\s*=\s*(\d+)")
     assert (max_small, split_min, t64_min, coop_min) == (4, 384, 2048, 256)
 
     def t64(c):
