@@ -1,14 +1,19 @@
 """The operators added after the core pipeline -- filter2d, composite_layers, grid_scatter, msi, transform_distort, the four
-geometry entry points, rasterize_layers -- through the ctypes binding of the C ABI with every output and workspace between
-sentinel elements (DRTK_CAPI_GUARD, drtk_amd/capi.py `_out`): a fixed list of small cases, each the smallest that still ends
-in a ragged tail at the end of a tensor, each compared with its oracle under the bounds of that operator's GPU tests (the
-guard also leaves every output merely element-aligned: those paths must be right, not only in bounds), and after each
+geometry entry points, rasterize_layers, the image losses (ssim, photometric_loss), mipmap_pyramid -- through the ctypes
+binding of the C ABI with every output and workspace between sentinel elements (DRTK_CAPI_GUARD, drtk_amd/capi.py `_out`): a
+fixed list of small cases, each the smallest that still ends in a ragged tail at the end of a tensor, each compared with its
+oracle under the bounds of that operator's GPU tests (the guard also leaves every output merely element-aligned: those
+paths must be right, not only in bounds), and after each
 `capi.check_guards()`.  Not collected by pytest; tests/test_gpu_parity.py starts it in a child process:
 
     DRTK_CAPI_GUARD=1 DRTK_CAPI_POISON=1 python tests/guarded_added_ops.py [--only NAME]
     python tests/guarded_added_ops.py --list                (no GPU needed)
 
-The first case shows that a damaged guard is reported.  Oracles, bounds and helpers are those of the operators' own test
+The first case shows that a damaged guard is reported.  The image losses run their structural cases (interior tiles; 256,
+257, 297 and 513 partial sums in the slot workspace, whose size drtk_amd_image_loss_workspace_bytes gave), both precisions
+and paddings, plain and weighted, forward with the gradient maps and backward; mipmap_pyramid the ragged shapes of its test
+module at full depth, every level and grad_input element-aligned at once, with all gradients and with one absent; then the
+first 20 seeds of tests/fuzz_image_ops.py.  Oracles, bounds and helpers are those of the operators' own test
 modules, which this script imports.  Left out: what the torch operators allocate in C++ (only the binding has guards) and
 grad_grid of grid_scatter (allocated with the grid's strides, outside `_out`)."""
 import argparse
@@ -159,8 +164,48 @@ def rasterize_layers_case(scene, K):
     T.check_order(*got)
 
 
+# ---- image losses, mipmap_pyramid ------------------------------------------------------------------------------------------------
+def image_loss_case(name, padding, weighted, dtype):
+    import image_loss_oracle as O
+    import test_gpu_image_loss as T
+
+    shape, k, paddings, _ = O.STRUCTURAL_CASES[name]
+    assert padding in paddings
+    T.check_c_abi_case(shape, k, padding, weighted, dtype)  # the map, both means, their maps [3,N,C,OH,OW] and all three backward calls
+
+
+# of its SHAPES, those with partial tiles: odd on both axes, odd drops inside a tile, a partial last tile of many, 11 levels
+MIPMAP_PYRAMID_SHAPES = [(1, 1, 65, 63), (2, 3, 70, 130), (1, 1, 36, 4100), (1, 1, 1100, 1030)]
+
+
+def mipmap_pyramid_case(shape, dtype, absent):
+    import test_gpu_mipmap_pyramid as T
+    from drtk_amd import capi
+
+    assert shape in T.SHAPES and (shape[2] % 64 or shape[3] % 64)
+    x, want, grads, want_grad = T.problem(shape, None, dtype)
+    assert len(want) == T.max_levels(*shape[2:]) > absent >= 0
+    out = capi.mipmap_pyramid(x, len(want))
+    for l, (a, b) in enumerate(zip(out, want)):
+        assert a.shape == b.shape and th.equal(a, b), f"level {l}"
+    assert th.equal(capi.mipmap_pyramid_backward(grads), want_grad)
+    some = [None if l == absent else g for l, g in enumerate(grads)]
+    assert th.equal(capi.mipmap_pyramid_backward(some, grad_input=capi._out(*shape, dtype=dtype, device=DEV)), T.recurrence(some, x))
+
+
+def fuzz_image_ops_case(seed):
+    import fuzz_image_ops as F
+
+    c = F.make_case(seed)
+    try:
+        F.run_case(c, check_guards=False)  # they are checked, and counted, after the case
+    except AssertionError as e:
+        raise AssertionError(f"{F.describe(c)}: {e}") from e
+
+
 def cases():
     """[(name, function, arguments)], in the order they run"""
+    import image_loss_oracle
     import msi_oracle
     import test_gpu_composite_layers as TC
     import test_gpu_geometry as TG
@@ -187,6 +232,18 @@ def cases():
     for scene in ("ragged_f32", "edge_cases_f32"):
         for K in (1, 3, 8):
             out.append((f"rasterize_layers/{scene}/K{K}", rasterize_layers_case, (scene, K)))
+    for name, (_, _, paddings, _) in image_loss_oracle.STRUCTURAL_CASES.items():
+        if name == "five_by_two":  # the interior-tile case and the slot cases: every tile kind and every pass of the finalize kernel
+            continue
+        for padding in paddings:
+            for weighted in (False, True):
+                for dtype in (F32, F64):
+                    out.append((f"image_loss/{name}/{padding}/{'weighted' if weighted else 'plain'}/{TAG[dtype]}", image_loss_case, (name, padding, weighted, dtype)))
+    for i, shape in enumerate(MIPMAP_PYRAMID_SHAPES):
+        for dtype in (F32, F64):
+            out.append((f"mipmap_pyramid/{'x'.join(map(str, shape))}/{TAG[dtype]}", mipmap_pyramid_case, (shape, dtype, (0, 1, 3, 7)[i])))
+    for seed in range(20):
+        out.append((f"fuzz_image_ops/seed{seed}", fuzz_image_ops_case, (seed,)))
     assert len({c[0] for c in out}) == len(out)
     return out
 

@@ -1,7 +1,8 @@
 """The definition of `drtk_amd.ssim` / `drtk_amd.photometric_loss` restated with PyTorch's own pieces, in the dtype of its
 inputs (float64 for the checks, float32 for the error of the formulation itself) on whatever device they live on: grouped
 `conv2d`, row then column.  `gradient()` is the closed form the backward kernel evaluates; tests/test_image_loss_host.py
-holds it against autograd of the forward here.  Also the seeded inputs the tests and profiles/image_loss_bench.py share."""
+holds it against autograd of the forward here.  Also the seeded inputs the tests and profiles/image_loss_bench.py share,
+and the structural cases (STRUCTURAL_CASES) that the GPU tests, the guarded driver and the host test have in common."""
 import torch as th
 import torch.nn.functional as F
 
@@ -121,6 +122,56 @@ def make_images(shape, seed=0, dtype=th.float64, data_range=1.0, device="cpu"):
     target[:, :, :max(H // 3, 1)] = 0.4
     img = (target + 0.1 * th.randn(shape, generator=gen, dtype=th.float64)).clamp(0, 1)
     return (img * data_range).to(dtype).to(device), (target * data_range).to(dtype).to(device)
+
+
+def make_distinct_views(shape, seed=0, dtype=th.float64, data_range=1.0, device="cpu", noise=0.03):
+    """(img, target) for the cases with many partial sums, where ONE view's share of a mean of up to 513 views must stand
+    100 x above the float32 tolerance (tests/test_image_loss_host.py holds them to that).  `make_images` cannot deliver it
+    at any noise, for two reasons this removes.  Its views have nearly the same statistics, so leaving one out moves a mean
+    of N views by far less than 1 / N.  And where its target is flat B2 falls to C2, where the float32 formulation is off by
+    1e-4: that error sets the tolerance, and 400 x 1e-4 is more than any view of 257 can move a mean.
+    Here the target is a checkerboard of dark [0, 0.2] and bright [0.8, 1] pixels, each with a value of its own: every
+    window, also the narrow one of window_size 3, holds both, so B2 stays near 0.2 and the formulation's error near 1e-6.
+    In the even views img is the target plus Gaussian noise, S near 1; in the odd views it is the NEGATIVE of the target plus
+    noise, S near -0.6 and |x - y| near 0.8: every view is about 0.8 from the mean of S."""
+    N, C, H, W = shape
+    gen = th.Generator().manual_seed(seed)
+    yy, xx = th.arange(H).view(1, 1, H, 1), th.arange(W).view(1, 1, 1, W)
+    bright = ((yy + xx) % 2 == 0).to(th.float64)
+    target = 0.2 * th.rand(shape, generator=gen, dtype=th.float64) + 0.8 * bright
+    flip = (th.arange(N) % 2 == 1).view(N, 1, 1, 1)
+    img = (th.where(flip, 1.0 - target, target) + noise * th.randn(shape, generator=gen, dtype=th.float64)).clamp(0, 1)
+    return (img * data_range).to(dtype).to(device), (target * data_range).to(dtype).to(device)
+
+
+# The structural cases of the GPU tests, of tests/guarded_added_ops.py and of the host test that proves what they reach:
+# name -> (shape, window_size, paddings, inputs).  Each is the smallest shape that reaches its path: a tile of the kernels
+# is 32 x 32, an interior tile needs three on an axis, the one-workgroup finalize kernel takes 256 slots per pass.
+STRUCTURAL_CASES = {
+    "interior_tiles": ((1, 2, 97, 99), 11, ("same", "valid"), "images"),  # 4 x 4 tiles; "valid": 87 x 89, 3 x 3, one true interior tile
+    "five_by_two": ((2, 1, 40, 131), 3, ("same", "valid"), "images"),     # tiles_x = 5 != tiles_y = 2, two views
+    "slots256": ((256, 1, 8, 9), 3, ("same",), "distinct_views"),         # a tile per view: the finalize loop ends after one pass
+    "slots257": ((257, 1, 8, 9), 3, ("same",), "distinct_views"),         # thread 0 takes a second slot
+    "slots513": ((513, 1, 8, 9), 3, ("same",), "distinct_views"),         # ... and a third: the order within a thread
+    "tiles_and_views": ((33, 1, 75, 75), 11, ("same", "valid"), "distinct_views"),  # 3 x 3 tiles x 33 views = 297 slots
+}
+SLOT_CASES = [name for name, c in STRUCTURAL_CASES.items() if c[3] == "distinct_views"]
+MAKERS = {(c[0], c[1]): c[3] for c in STRUCTURAL_CASES.values()}
+
+
+def case_inputs(shape, k, dtype=th.float64, data_range=1.0, device="cpu"):
+    """(img, target) of the case (shape, window_size): `make_distinct_views` for the many-slot cases, `make_images` otherwise."""
+    maker = make_distinct_views if MAKERS.get((tuple(shape), k)) == "distinct_views" else make_images
+    return maker(tuple(shape), seed=sum(shape) + k, dtype=dtype, data_range=data_range, device=device)
+
+
+def tile_constants(root):
+    """(kIlTileW, kIlTileH, kIlSums, kBlock) as drtk_amd/csrc spells them."""
+    import os
+    import re
+
+    src = open(os.path.join(root, "drtk_amd", "csrc", "image_loss.hip")).read() + open(os.path.join(root, "drtk_amd", "csrc", "common.hpp")).read()
+    return tuple(int(re.search(rf"constexpr int {name} = (\d+);", src).group(1)) for name in ("kIlTileW", "kIlTileH", "kIlSums", "kBlock"))
 
 
 def make_mask(shape, seed=0, device="cpu"):

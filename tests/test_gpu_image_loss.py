@@ -1,6 +1,8 @@
 """GPU (-m gpu): `drtk_amd.ssim` / `drtk_amd.photometric_loss` and the C ABI binding against tests/image_loss_oracle.py run on
 the device -- float64 to 1e-12 on every shape (index, halo and tile mistakes), float32 within 4 x the error of the float32
-PyTorch formulation itself, weights, layouts, reproducibility, autocast, poisoned outputs, graph capture, errors."""
+PyTorch formulation itself, weights, layouts, reproducibility, autocast, poisoned outputs, graph capture, errors.  The shapes
+include interior tiles in both axes under both paddings and 256, 257, 297 and 513 partial sums (the finalize kernel takes 256
+a pass); random shapes are in tests/test_gpu_fuzz_image_ops.py."""
 import functools
 import os
 import re
@@ -34,6 +36,11 @@ CASES = [
     ((1, 2, 40, 40), 3, 1.0), ((1, 2, 40, 40), 5, 1.0), ((1, 2, 40, 40), 15, 1.0),
 ]
 PARAMS = [(*c, p, w) for c in CASES for p in ("same", "valid") if p == "same" or min(c[0][2:]) >= c[1] for w in (False, True)]
+# Past a 2 x 2 tile grid and past the 256 slots one pass of the finalize kernel takes (image_loss_oracle.STRUCTURAL_CASES;
+# tests/test_image_loss_host.py proves the tile grids and slot counts, and that one view left out of a many-slot case moves
+# each scalar by more than 100 x the float32 tolerance below)
+STRUCTURAL = {name: [(shape, k, 1.0, p, w) for p in paddings for w in (False, True)] for name, (shape, k, paddings, _) in O.STRUCTURAL_CASES.items()}
+PARAMS += [q for params in STRUCTURAL.values() for q in params]
 IDS = [f"{'x'.join(map(str, s))}-w{k}-r{int(dr)}-{p}-{'weighted' if w else 'plain'}" for s, k, dr, p, w in PARAMS]
 L1W, SSW = 0.7, 0.3
 
@@ -42,7 +49,7 @@ L1W, SSW = 0.7, 0.3
 def problem(shape, k, data_range, padding, weighted):
     """Inputs (float32 values, so that both precisions see the same numbers) and the float64 oracle's results on the device,
     computed once and never modified: the map, an upstream gradient for it, its gradient, the two scalars, their gradients."""
-    x32, y32 = O.make_images(shape, seed=sum(shape) + k, dtype=th.float32, data_range=data_range, device=DEV)
+    x32, y32 = O.case_inputs(shape, k, dtype=th.float32, data_range=data_range, device=DEV)
     w = O.make_mask(shape, seed=k, device=DEV) if weighted else None
     kw = dict(window_size=k, sigma=1.5 * k / 11, data_range=data_range, padding=padding)
     x, y = x32.double(), y32.double()
@@ -85,33 +92,42 @@ def ours(x, y, w, kw, h):
     return out
 
 
+def ours_c_abi(x, y, w, kw, h):
+    """The same quantities through the ctypes binding of the C ABI (poisoned outputs, and guards around them where asked for),
+    with the scalars the forward leaves in device memory: `scalars_ssim`, `scalars_photo`."""
+    from drtk_amd import capi
+
+    cw = dict(window_size=kw["window_size"], sigma=kw["sigma"], data_range=kw["data_range"], valid=kw["padding"] == "valid")
+    S, maps, scalars = capi.image_loss_forward(x, y, None, mode="map", with_maps=True, **cw)
+    assert scalars is None
+    out = dict(map=S, grad_map=capi.image_loss_backward(x, y, None, maps, h.to(x.dtype), None, mode="map", **cw))
+    one = th.ones((), dtype=x.dtype, device=x.device)
+    for name, mode in (("ssim", "ssim"), ("photo", "photometric")):
+        cm = dict(cw, mode=mode, l1_weight=L1W, ssim_weight=SSW)
+        v, maps, scalars = capi.image_loss_forward(x, y, w, with_maps=True, **cm)
+        assert v.ndim == 0 and v.dtype == x.dtype and scalars.dtype == th.float64
+        out[name], out["grad_" + name], out["scalars_" + name] = v, capi.image_loss_backward(x, y, w, maps, one, scalars, **cm), scalars
+    return out
+
+
 def err(a, b):
     return float((a.double() - b.double()).abs().max())
 
 
-@pytest.mark.parametrize("shape,k,data_range,padding,weighted", PARAMS, ids=IDS)
-def test_float64_against_the_oracle(shape, k, data_range, padding, weighted):
-    """Map, both scalars and every gradient within 1e-12 * max(1, max|ref|): the two differ by summation order only."""
-    p = problem(shape, k, data_range, padding, weighted)
-    got, ref = ours(p["x"], p["y"], p["w"], p["kw"], p["h"]), p["ref"]
-    for name in ("map", "ssim", "photo", "grad_map", "grad_ssim", "grad_photo"):
+QUANTITIES = ("map", "ssim", "photo", "grad_map", "grad_ssim", "grad_photo")
+
+
+def check_float64(got, ref):
+    for name in QUANTITIES:
         assert got[name].shape == ref[name].shape, name
         e, top = err(got[name], ref[name]), max(1.0, float(ref[name].abs().max()))
         print(f"float64 {name}: max abs err {e:.3e}, max |ref| {top:.3e}")
         assert e <= 1e-12 * top, (name, e, top)
 
 
-@pytest.mark.parametrize("shape,k,data_range,padding,weighted", PARAMS, ids=IDS)
-def test_float32_within_four_times_the_formulations_own_error(shape, k, data_range, padding, weighted):
-    """The bar per case: the error of the float32 PyTorch formulation (the oracle in float32 on this device) against the
-    float64 oracle, maxima over elements, maps and gradients separately; the kernels stay within 4 x that (another
-    summation order, fused multiply-adds).  The scalars are means of the map's elements (sums in double) and of |x - y|: no
-    further off than 4 x the formulation's worst map element, plus 4 eps of the data range for the L1 term."""
-    p = problem(shape, k, data_range, padding, weighted)
-    ref = p["ref"]
-    form = reference(p["x32"], p["y32"], p["w"], p["kw"], th.float32, h=p["h"])
-    got = ours(p["x32"], p["y32"], p["w"], p["kw"], p["h"])
+def check_float32(got, ref, form, data_range):
     for name in ("map", "grad_map", "grad_ssim", "grad_photo"):
+        assert got[name].shape == ref[name].shape, name
         bar, e = err(form[name], ref[name]), err(got[name], ref[name])
         print(f"float32 {name}: kernel {e:.3e}, formulation {bar:.3e}, ratio {e / bar if bar else float('inf'):.2f}")
         assert e <= 4 * bar, (name, e, bar)
@@ -120,6 +136,34 @@ def test_float32_within_four_times_the_formulations_own_error(shape, k, data_ran
         e = err(got[name], ref[name])
         print(f"float32 {name}: kernel {e:.3e}, formulation {err(form[name], ref[name]):.3e}, bound {tol:.3e}")
         assert e <= tol, (name, e, tol)
+
+
+def check_case(shape, k, data_range, padding, weighted, dtype, api=ours):
+    """One case in one precision through `api` (`ours`, `ours_c_abi`) under this file's two bounds; -> what `api` returned."""
+    p = problem(shape, k, data_range, padding, weighted)
+    if dtype == th.float64:
+        got = api(p["x"], p["y"], p["w"], p["kw"], p["h"])
+        check_float64(got, p["ref"])
+    else:
+        form = reference(p["x32"], p["y32"], p["w"], p["kw"], th.float32, h=p["h"])
+        got = api(p["x32"], p["y32"], p["w"], p["kw"], p["h"])
+        check_float32(got, p["ref"], form, data_range)
+    return got
+
+
+@pytest.mark.parametrize("shape,k,data_range,padding,weighted", PARAMS, ids=IDS)
+def test_float64_against_the_oracle(shape, k, data_range, padding, weighted):
+    """Map, both scalars and every gradient within 1e-12 * max(1, max|ref|): the two differ by summation order only."""
+    check_case(shape, k, data_range, padding, weighted, th.float64)
+
+
+@pytest.mark.parametrize("shape,k,data_range,padding,weighted", PARAMS, ids=IDS)
+def test_float32_within_four_times_the_formulations_own_error(shape, k, data_range, padding, weighted):
+    """The bar per case: the error of the float32 PyTorch formulation (the oracle in float32 on this device) against the
+    float64 oracle, maxima over elements, maps and gradients separately; the kernels stay within 4 x that (another
+    summation order, fused multiply-adds).  The scalars are means of the map's elements (sums in double) and of |x - y|: no
+    further off than 4 x the formulation's worst map element, plus 4 eps of the data range for the L1 term."""
+    check_case(shape, k, data_range, padding, weighted, th.float32)
 
 
 BASE = ((2, 3, 37, 53), 11, 1.0)
@@ -161,21 +205,36 @@ def test_weights(padding):
 @pytest.mark.parametrize("dtype", [th.float32, th.float64], ids=["f32", "f64"])
 @pytest.mark.parametrize("padding", ["same", "valid"])
 def test_all_zero_weight_gives_zero_without_nan(padding, dtype):
-    """Both means are exactly 0 (photometric_loss is then the constant ssim_weight) and the gradient is exactly 0, all finite."""
+    """Both means are exactly 0 (photometric_loss is then the constant ssim_weight) and the gradient is exactly 0, all finite
+    -- also with 257 partial sums, where the finalize kernel takes a second pass.  There, with a weight in the last view
+    alone, the one live slot is the one that pass reaches: the results are those of the last view by itself, bit for bit
+    (every other slot adds an exact zero), and they are not zero."""
     import drtk_amd
 
-    shape, k, _ = BASE
-    p = problem(shape, k, 1.0, padding, False)
-    x, y = p["x"].to(dtype), p["y"].to(dtype)
-    for zero in (th.zeros(shape[0], *shape[2:], dtype=th.bool, device=DEV), th.zeros(shape[0], 1, *shape[2:], dtype=dtype, device=DEV)):
-        for fn, want in ((lambda a: drtk_amd.ssim(a, y, zero, **p["kw"]), 0.0),
-                         (lambda a: drtk_amd.photometric_loss(a, y, zero, 1.0, 0.0, **p["kw"]), 0.0),
-                         (lambda a: drtk_amd.photometric_loss(a, y, zero, 0.8, 0.25, **p["kw"]), 0.25)):
-            leaf = x.clone().requires_grad_(True)
-            v = fn(leaf)
-            v.backward()
-            assert float(v.detach()) == want
-            assert bool(th.isfinite(leaf.grad).all()) and not bool(leaf.grad.any())
+    many, k3, _, _ = O.STRUCTURAL_CASES["slots257"]
+    for shape, k in (BASE[:2], (many, k3)):
+        p = problem(shape, k, 1.0, padding, False)
+        x, y = p["x"].to(dtype), p["y"].to(dtype)
+        for zero in (th.zeros(shape[0], *shape[2:], dtype=th.bool, device=DEV), th.zeros(shape[0], 1, *shape[2:], dtype=dtype, device=DEV)):
+            for fn, want in ((lambda a: drtk_amd.ssim(a, y, zero, **p["kw"]), 0.0),
+                             (lambda a: drtk_amd.photometric_loss(a, y, zero, 1.0, 0.0, **p["kw"]), 0.0),
+                             (lambda a: drtk_amd.photometric_loss(a, y, zero, 0.8, 0.25, **p["kw"]), 0.25)):
+                leaf = x.clone().requires_grad_(True)
+                v = fn(leaf)
+                v.backward()
+                assert float(v.detach()) == want
+                assert bool(th.isfinite(leaf.grad).all()) and not bool(leaf.grad.any())
+    last = many[0] - 1
+    assert last == 256
+    for live in (O.make_mask((1, *many[1:]), seed=5, device=DEV), th.rand(1, 1, *many[2:], generator=th.Generator().manual_seed(4), dtype=th.float64).to(dtype).to(DEV) + 0.25):
+        w = th.zeros(many[0], *live.shape[1:], dtype=live.dtype, device=DEV)
+        w[last] = live[0]
+        for fn in (drtk_amd.ssim, lambda a, b, c, **kw: drtk_amd.photometric_loss(a, b, c, L1W, SSW, **kw)):
+            leaf, alone = x.clone().requires_grad_(True), x[last:].clone().requires_grad_(True)
+            v, v1 = fn(leaf, y, w, **p["kw"]), fn(alone, y[last:], live, **p["kw"])
+            v.backward(), v1.backward()
+            assert th.equal(v.detach(), v1.detach()) and float(v.detach()) != 0.0 and bool(th.isfinite(v.detach()))
+            assert th.equal(leaf.grad[last:], alone.grad) and bool(alone.grad.any()) and not bool(leaf.grad[:last].any())
 
 
 @pytest.mark.parametrize("dtype", [th.float32, th.float64], ids=["f32", "f64"])
@@ -281,6 +340,37 @@ def test_c_abi_binding_writes_every_element_and_nothing_stray(padding, dtype):
         leaf = x.clone().requires_grad_(True)
         drtk_amd.photometric_loss(leaf, y, w, L1W, SSW, **kw).backward()
         assert bool(th.isfinite(g).all()) and th.equal(g, leaf.grad)
+
+
+def check_c_abi_case(shape, k, padding, weighted, dtype):
+    """A case through the binding under this file's bounds (shared with tests/guarded_added_ops.py); where the forward leaves
+    scalars they are finite and those of the Python API: ssim, and the l1 that photometric_loss(1, 0) returns by itself."""
+    import drtk_amd
+
+    got = check_case(shape, k, 1.0, padding, weighted, dtype, api=ours_c_abi)
+    p = problem(shape, k, 1.0, padding, weighted)
+    x, y = (p["x"], p["y"]) if dtype == th.float64 else (p["x32"], p["y32"])
+    py = ours(x, y, p["w"], p["kw"], p["h"])
+    for name in QUANTITIES:
+        assert bool(th.isfinite(got[name]).all()) and th.equal(got[name], py[name]), name
+    ssim, l1 = drtk_amd.ssim(x, y, p["w"], **p["kw"]), drtk_amd.photometric_loss(x, y, p["w"], 1.0, 0.0, **p["kw"])
+    for name in ("scalars_ssim", "scalars_photo"):
+        s = got[name]
+        assert s.shape == (4,) and bool(th.isfinite(s).all()), (name, s)
+        assert th.equal(s[0].to(dtype), ssim) and bool(s[2] > 0), (name, s, ssim)
+    s = got["scalars_photo"]
+    assert th.equal(s[1].to(dtype), l1) and bool(s[3] > 0) and th.equal(s[0], got["scalars_ssim"][0]), (s, l1)
+
+
+SLOT_PARAMS = [(name, p) for name in O.SLOT_CASES for p in O.STRUCTURAL_CASES[name][2]]
+
+
+@pytest.mark.parametrize("dtype", [th.float32, th.float64], ids=["f32", "f64"])
+@pytest.mark.parametrize("name,padding", SLOT_PARAMS, ids=[f"{n}-{p}" for n, p in SLOT_PARAMS])
+def test_c_abi_binding_with_more_slots_than_one_finalize_pass_takes(name, padding, dtype):
+    """The many-slot cases through capi, weighted: the bounds of this file, bit for bit the Python API, scalars finite."""
+    shape, k, _, _ = O.STRUCTURAL_CASES[name]
+    check_c_abi_case(shape, k, padding, True, dtype)
 
 
 def test_graph_capture_of_forward_and_backward():

@@ -1,6 +1,8 @@
 """CPU: `ssim` and `photometric_loss` without a GPU -- the feature is present at every layer of the interface (Python export,
 operator schemas and dispatch keys, the loud failure on CPU tensors, the argument errors, the C ABI's argument validation),
-and the closed-form gradient its backward kernel evaluates is autograd of the definition (tests/image_loss_oracle.py)."""
+and the closed-form gradient its backward kernel evaluates is autograd of the definition (tests/image_loss_oracle.py).  Then
+what the GPU tests rely on: the structural cases have the tile grids and slot counts they claim, one view left out of a
+many-slot case moves each scalar by more than 100 tolerances, and the fuzzer's seeds hold what their test says."""
 import ctypes
 import inspect
 
@@ -179,6 +181,130 @@ def test_c_abi_argument_validation_without_gpu():
     assert fwd(out=z) == -1 and fwd(scalars=z) == -1 and fwd(wsp=z) == -1
     assert fwd(nbytes=8) == -2  # workspace too small
     assert bwd(maps=z) == -1 and bwd(gout=z) == -1 and bwd(gimg=z) == -1 and bwd(scalars=z) == -1
+
+
+def _grid(shape, k, padding):
+    """(tiles_x, tiles_y, slots) of the forward, the slots from the library's own workspace size."""
+    from conftest import ROOT
+    from drtk_amd import capi
+
+    TW, TH, sums, _ = O.tile_constants(ROOT)
+    N, _, H, W = shape
+    off = k // 2 if padding == "valid" else 0
+    nbytes = capi.image_loss_workspace_bytes(N, H, W, k, padding == "valid")
+    assert nbytes % (sums * 8) == 0
+    return -(-(W - 2 * off) // TW), -(-(H - 2 * off) // TH), nbytes // (sums * 8)
+
+
+def test_structural_cases_reach_the_tiles_and_slot_counts_they_are_there_for():
+    """What tests/test_gpu_image_loss.py, tests/guarded_added_ops.py and image_loss_oracle.STRUCTURAL_CASES say of these
+    cases, from the tile constants in csrc/image_loss.hip and drtk_amd_image_loss_workspace_bytes: a change of the tile
+    size or of the finalize kernel's width fails here instead of quietly leaving a path without a test."""
+    import test_gpu_image_loss as G
+    from conftest import ROOT
+
+    TW, TH, _, block = O.tile_constants(ROOT)
+    S = O.STRUCTURAL_CASES
+    grids = {(name, p): _grid(S[name][0], S[name][1], p) for name in S for p in S[name][2]}
+    for (name, p), (tx, ty, slots) in grids.items():
+        assert slots == S[name][0][0] * tx * ty, (name, p)
+        for weighted in (False, True):  # and the GPU tests run them
+            assert (S[name][0], S[name][1], 1.0, p, weighted) in G.PARAMS, (name, p)
+    # interior tiles: one with a neighbour on either side, in x and in y, under both paddings -- in "valid" exactly one
+    assert grids[("interior_tiles", "same")] == (4, 4, 16) and grids[("interior_tiles", "valid")] == (3, 3, 9)
+    shape, k = S["interior_tiles"][:2]
+    assert (-(-shape[3] // TW), -(-shape[2] // TH)) == (4, 4)  # the backward's tiles, over the image
+    assert (shape[3] - 2 * (k // 2)) % TW != 0 and (shape[2] - 2 * (k // 2)) % TH != 0  # with ragged last tiles
+    # more tiles across than down, more than one view
+    assert grids[("five_by_two", "same")] == (5, 2, 20) and grids[("five_by_two", "valid")] == (5, 2, 20)
+    # the finalize kernel: `block` threads, thread t takes slots t, t + block, ...
+    assert grids[("slots256", "same")] == (1, 1, block)          # one pass, every thread one slot
+    assert grids[("slots257", "same")] == (1, 1, block + 1)      # thread 0 takes a second
+    assert grids[("slots513", "same")] == (1, 1, 2 * block + 1)  # and a third
+    assert grids[("tiles_and_views", "same")] == (3, 3, 297) and grids[("tiles_and_views", "valid")] == (3, 3, 297)
+    assert block < 297 < 2 * block
+    assert O.SLOT_CASES == ["slots256", "slots257", "slots513", "tiles_and_views"]
+
+
+SLOT_PARAMS = [(name, p) for name in O.SLOT_CASES for p in O.STRUCTURAL_CASES[name][2]]
+
+
+@pytest.mark.parametrize("name,padding", SLOT_PARAMS, ids=[f"{n}-{p}" for n, p in SLOT_PARAMS])
+def test_a_view_left_out_of_a_many_slot_case_moves_each_scalar_by_100_tolerances(name, padding):
+    """The condition under which a dropped or mis-owned slot shows in the GPU tests: with the weight of one view zeroed --
+    the last, a middle one, and the first of the finalize kernel's second pass -- `ssim` and `photometric_loss` (float64,
+    the oracle) move by more than 100 x the tolerance test_float32_within_four_times_the_formulations_own_error applies to
+    that scalar, plain and under the mask.  The tolerance is formed as there, from the float32 formulation's error on the map,
+    here on the CPU (another summation order in conv2d than on the device; the factor 100 is not that close, the least ratio
+    is 160).  In tiles_and_views a view is nine slots: there the weight of one tile of one view, the interior one, is zeroed too."""
+    import test_gpu_image_loss as G
+    from conftest import ROOT
+
+    shape, k, _, _ = O.STRUCTURAL_CASES[name]
+    N, _, H, W = shape
+    kw = dict(window_size=k, sigma=1.5 * k / 11, data_range=1.0, padding=padding)
+    x32, y32 = O.case_inputs(shape, k, dtype=th.float32)
+    x, y = x32.double(), y32.double()
+    map_bar = float((O.ssim(x32, y32, reduction="none", **kw).double() - O.ssim(x, y, reduction="none", **kw)).abs().max())
+    tol = {"ssim": 4 * map_bar, "photo": G.SSW * 4 * map_bar + G.L1W * 4 * th.finfo(th.float32).eps}
+
+    def scalars(w):
+        return {"ssim": float(O.ssim(x, y, w, **kw)), "photo": float(O.photometric_loss(x, y, w, G.L1W, G.SSW, **kw))}
+
+    TW, TH, _, block = O.tile_constants(ROOT)
+    off = k // 2 if padding == "valid" else 0
+    least = float("inf")
+    for w in (th.ones(N, H, W, dtype=th.float64), O.make_mask(shape, seed=k).double()):
+        full = scalars(w)
+        holes = [(v, slice(None), slice(None)) for v in sorted({N - 1, N // 2, min(block, N - 1)})]
+        if name == "tiles_and_views":
+            holes.append((N // 2, slice(off + TH, off + 2 * TH), slice(off + TW, off + 2 * TW)))
+        for v, rows, cols in holes:
+            wz = w.clone()
+            assert bool(wz[v, rows, cols].any())
+            wz[v, rows, cols] = 0
+            for q, value in scalars(wz).items():
+                ratio = abs(value - full[q]) / tol[q]
+                least = min(least, ratio)
+                assert ratio > 100, (name, padding, v, q, value, full[q], tol[q])
+    print(f"{name} {padding}: map_bar {map_bar:.3e}, least movement {least:.0f} tolerances")
+
+
+def test_fuzzer_seeds_of_the_suite_hold_what_the_gpu_test_says():
+    """tests/fuzz_image_ops.py, seeds 0 .. 239 (tests/test_gpu_fuzz_image_ops.py), from the drawn numbers alone: legal cases,
+    every operator, weight kind, layout, padding and precision, means over more than 256 views, interior tiles."""
+    import collections
+
+    import fuzz_image_ops as F
+    import test_gpu_fuzz_image_ops as G
+    from conftest import ROOT
+
+    TW, TH, _, block = O.tile_constants(ROOT)
+    cases = [F.make_case(seed) for seed in range(G.BLOCKS * G.PER_BLOCK)]
+    assert cases == [F.make_case(seed) for seed in range(G.BLOCKS * G.PER_BLOCK)] and len(cases) == 240  # seeded
+    ops = collections.Counter(c["op"] for c in cases)
+    assert set(ops) == set(F.OPS) and min(ops.values()) >= 50, ops
+    losses = [c for c in cases if c["op"] != "mipmap_pyramid"]
+    for c in losses:
+        assert 1 <= c["N"] <= 600 and 1 <= c["C"] <= 4 and 1 <= min(c["H"], c["W"]) and max(c["H"], c["W"]) <= 140, c
+        assert c["k"] % 2 == 1 and 3 <= c["k"] <= 15 and 0.5 <= c["sigma"] <= 3.0, c
+        assert c["padding"] == "same" or min(c["H"], c["W"]) >= c["k"], c
+        assert (c["weight"] == "none") or c["op"] != "ssim_map", c
+        assert c["N"] <= 6 or (c["N"] > block and max(c["H"], c["W"]) <= 12 and c["op"] != "ssim_map"), c
+    for key, values in (("weight", F.WEIGHTS), ("layout", F.LAYOUTS), ("padding", ("same", "valid")), ("dtype", ("f32", "f64")), ("data_range", (1.0, 255.0))):
+        assert {c[key] for c in losses} == set(values), key
+    assert {c["k"] for c in losses} == set(range(3, 16, 2))
+    assert sum(c["N"] > block for c in losses) == 7
+    across = lambda c, size, tile: -(-(size - (2 * (c["k"] // 2) if c["padding"] == "valid" else 0)) // tile)  # noqa: E731
+    assert sum(across(c, c["W"], TW) >= 3 for c in losses) >= 60 and sum(across(c, c["H"], TH) >= 3 for c in losses) >= 60
+    assert sum(c["padding"] == "valid" and across(c, c["W"], TW) >= 3 and across(c, c["H"], TH) >= 3 for c in losses) == 7
+    assert sum(1 in (c["H"], c["W"]) for c in losses) >= 20
+    pyramids = [c for c in cases if c["op"] == "mipmap_pyramid"]
+    for c in pyramids:
+        assert 1 <= c["N"] <= 3 and 1 <= c["C"] <= 5 and 1 <= min(c["H"], c["W"]) and max(c["H"], c["W"]) <= 200, c
+        assert 1 <= c["levels"] <= min(11, min(c["H"], c["W"]).bit_length()) and len(c["absent"]) < c["levels"], c
+    assert {c["layout"] for c in pyramids} == {"contiguous", "one_element_in"} and {c["dtype"] for c in pyramids} == {"f32", "f64"}
+    assert any(0 in c["absent"] for c in pyramids) and any(c["absent"] == () for c in pyramids) and max(c["levels"] for c in pyramids) >= 7
 
 
 CASES = [((2, 3, 37, 53), 11, 1.5, 1.0), ((1, 2, 20, 17), 7, 1.0, 255.0), ((1, 1, 7, 9), 11, 1.5, 1.0), ((1, 1, 15, 15), 15, 2.5, 1.0)]
