@@ -10,6 +10,7 @@
 #include <atomic>
 #include <stdint.h>
 #include <string>
+#include <type_traits>
 
 #include "drtk_amd.h"
 
@@ -172,15 +173,44 @@ template <typename P>
 inline P* advance_typed(P* p, int64_t elements) {
   return p ? p + elements : nullptr;
 }
-#define DRTK_FOR_VIEW_SLICES(N, n0, n, CALL)                                        \
-  if ((N) > kMaxViewsPerLaunch) {                                                    \
-    for (int64_t n0 = 0; n0 < (N); n0 += kMaxViewsPerLaunch) {                       \
-      const int64_t n = (N) - n0 < kMaxViewsPerLaunch ? (N) - n0 : kMaxViewsPerLaunch; \
-      const int rc_slice_ = (CALL);                                                  \
-      if (rc_slice_ != DRTK_OK) return rc_slice_;                                    \
-    }                                                                                \
-    return DRTK_OK;                                                                  \
+// What an entry point does with more than kMaxViewsPerLaunch views: f(n0, n) -- the entry itself on views [n0, n0 + n) -- for
+// consecutive slices of at most kMaxViewsPerLaunch views; the first status that is not DRTK_OK ends the call.
+template <typename F>
+int for_view_slices(int64_t N, F&& f) {
+  for (int64_t n0 = 0; n0 < N; n0 += kMaxViewsPerLaunch) {
+    const int rc = f(n0, N - n0 < kMaxViewsPerLaunch ? N - n0 : kMaxViewsPerLaunch);
+    if (rc != DRTK_OK) return rc;
   }
+  return DRTK_OK;
+}
+
+// ---- the entry points' shared argument rules ---------------------------------------------------------------------------------
+inline bool valid_dtype(drtk_dtype_t d) { return d == DRTK_F32 || d == DRTK_F64; }
+// f(float{}) or f(double{}): an entry point states its typed call once, in a generic lambda that begins
+// `using T = decltype(tag);`.  Any other dtype is DRTK_ERR_INVALID_ARGUMENT.
+template <typename F>
+int dispatch_dtype(drtk_dtype_t d, F&& f) {
+  if (d == DRTK_F32) return f(float{});
+  if (d == DRTK_F64) return f(double{});
+  return DRTK_ERR_INVALID_ARGUMENT;
+}
+// A run-time mode, flag or count as a compile-time constant: f(Int<V>{}) for the V of LO ... HI that equals v (the entry points
+// have checked the range; anything else takes HI).
+template <int V>
+using Int = std::integral_constant<int, V>;
+template <int LO, int HI, typename F>
+auto with_constant(int v, F&& f) {
+  if constexpr (LO == HI) {
+    return f(Int<LO>{});
+  } else {
+    if (v == LO) return f(Int<LO>{});
+    return with_constant<LO + 1, HI>(v, f);
+  }
+}
+// a per-view array is shared by all views (stride 0) or holds one view after the other (stride = one view's elements)
+inline bool bad_view_stride(int64_t sN, int64_t per_view) { return sN != 0 && sN != per_view; }
+// a negative size, or an image whose pixel index does not fit 31 bits
+inline bool bad_image(int64_t N, int64_t H, int64_t W) { return N < 0 || H < 0 || W < 0 || H * W >= (int64_t(1) << 31); }
 
 // Per-kernel timing for benchmarks (include/drtk_amd.h: drtk_amd_kernel_timing_begin / _report).  Every launch of
 // the library goes through DRTK_LAUNCH; while a collection is open the launch is bracketed by two HIP events on its

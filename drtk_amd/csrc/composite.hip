@@ -296,10 +296,10 @@ __global__ __launch_bounds__(kBlock) void composite_backward_kernel(const Compos
 
 int composite_validate(drtk_dtype_t dtype, int64_t N, int64_t K, int64_t C, int64_t H, int64_t W) {
   constexpr int64_t kLimit = int64_t(1) << 31;
-  if (dtype != DRTK_F32 && dtype != DRTK_F64) return DRTK_ERR_INVALID_ARGUMENT;
-  if (N < 0 || C < 0 || H < 0 || W < 0 || C >= kLimit || H >= kLimit || W >= kLimit) return DRTK_ERR_INVALID_ARGUMENT;
+  if (!valid_dtype(dtype)) return DRTK_ERR_INVALID_ARGUMENT;
+  // (H and W also one by one: an empty image of 2^31 rows is invalid here)
+  if (C < 0 || C >= kLimit || H >= kLimit || W >= kLimit || bad_image(N, H, W)) return DRTK_ERR_INVALID_ARGUMENT;
   if (K < 1 || K > DRTK_AMD_MAX_RASTER_LAYERS) return DRTK_ERR_INVALID_ARGUMENT;
-  if (H * W >= kLimit) return DRTK_ERR_INVALID_ARGUMENT;
   if (N > 0 && H * W > 0 && C < 1) return DRTK_ERR_INVALID_ARGUMENT;
   return DRTK_OK;
 }
@@ -367,24 +367,20 @@ extern "C" int drtk_amd_composite_layers(
   if (!color || !alpha || !img || !transmittance || !strides_ok(color_strides, 3) || !strides_ok(alpha_strides, 2) || background_sN < 0)
     return DRTK_ERR_INVALID_ARGUMENT;
   const size_t es = dtype_size(dtype);
-  DRTK_FOR_VIEW_SLICES(
-      N, n0, n,
-      drtk_amd_composite_layers(
-          dtype, advance(color, n0 * color_strides[0], es), color_strides, advance(alpha, n0 * alpha_strides[0], es), alpha_strides,
-          advance_typed(index_img, n0 * K * H * W), advance(background, n0 * background_sN, es), background_sN, n, K, C, H, W,
-          advance(img, n0 * C * H * W, es), advance(transmittance, n0 * H * W, es), stream));
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == DRTK_F32) {
-    auto a = composite_inputs<float>(color, color_strides, alpha, alpha_strides, index_img, background, background_sN, C, H * W);
-    a.img = static_cast<float*>(img), a.trans = static_cast<float*>(transmittance);
-    composite_launch<float, false>(a, static_cast<int>(K), N, W, s);
-  } else {
-    auto a = composite_inputs<double>(color, color_strides, alpha, alpha_strides, index_img, background, background_sN, C, H * W);
-    a.img = static_cast<double*>(img), a.trans = static_cast<double*>(transmittance);
-    composite_launch<double, false>(a, static_cast<int>(K), N, W, s);
-  }
-  DRTK_RETURN_IF_LAUNCH_FAILED();
-  return DRTK_OK;
+  if (N > kMaxViewsPerLaunch) return for_view_slices(N, [&](int64_t n0, int64_t n) {
+    return drtk_amd_composite_layers(
+        dtype, advance(color, n0 * color_strides[0], es), color_strides, advance(alpha, n0 * alpha_strides[0], es), alpha_strides,
+        advance_typed(index_img, n0 * K * H * W), advance(background, n0 * background_sN, es), background_sN, n, K, C, H, W,
+        advance(img, n0 * C * H * W, es), advance(transmittance, n0 * H * W, es), stream);
+  });
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    auto a = composite_inputs<T>(color, color_strides, alpha, alpha_strides, index_img, background, background_sN, C, H * W);
+    a.img = static_cast<T*>(img), a.trans = static_cast<T*>(transmittance);
+    composite_launch<T, false>(a, static_cast<int>(K), N, W, static_cast<hipStream_t>(stream));
+    DRTK_RETURN_IF_LAUNCH_FAILED();
+    return DRTK_OK;
+  });
 }
 
 extern "C" int drtk_amd_composite_layers_backward(
@@ -402,31 +398,24 @@ extern "C" int drtk_amd_composite_layers_backward(
   if (grad_background && !background) return DRTK_ERR_INVALID_ARGUMENT;
   if (!grad_color && !grad_alpha && !grad_background) return DRTK_OK; // nothing is wanted
   const size_t es = dtype_size(dtype);
-  DRTK_FOR_VIEW_SLICES(
-      N, n0, n,
-      drtk_amd_composite_layers_backward(
-          dtype, advance(grad_img, n0 * C * H * W, es), advance(grad_transmittance, n0 * H * W, es),
-          advance(color, n0 * color_strides[0], es), color_strides, advance(alpha, n0 * alpha_strides[0], es), alpha_strides,
-          advance_typed(index_img, n0 * K * H * W), advance(background, n0 * background_sN, es), background_sN, n, K, C, H, W,
-          advance(grad_color, grad_color ? n0 * grad_color_strides[0] : 0, es), grad_color_strides,
-          advance(grad_alpha, grad_alpha ? n0 * grad_alpha_strides[0] : 0, es), grad_alpha_strides,
-          advance(grad_background, n0 * C * H * W, es), stream));
-  hipStream_t s = static_cast<hipStream_t>(stream);
-#define COMPOSITE_BWD(T)                                                                                                       \
-  do {                                                                                                                         \
-    auto a = composite_inputs<T>(color, color_strides, alpha, alpha_strides, index_img, background, background_sN, C, H * W);  \
-    a.g_img = static_cast<const T*>(grad_img), a.g_T = static_cast<const T*>(grad_transmittance);                              \
-    a.g_color = static_cast<T*>(grad_color), a.g_alpha = static_cast<T*>(grad_alpha), a.g_bg = static_cast<T*>(grad_background); \
-    if (grad_color) a.gc_sN = grad_color_strides[0], a.gc_sK = grad_color_strides[1], a.gc_sC = grad_color_strides[2];         \
-    if (grad_alpha) a.ga_sN = grad_alpha_strides[0], a.ga_sK = grad_alpha_strides[1];                                          \
-    composite_launch<T, true>(a, static_cast<int>(K), N, W, s);                                                                \
-  } while (0)
-  if (dtype == DRTK_F32) {
-    COMPOSITE_BWD(float);
-  } else {
-    COMPOSITE_BWD(double);
-  }
-#undef COMPOSITE_BWD
-  DRTK_RETURN_IF_LAUNCH_FAILED();
-  return DRTK_OK;
+  if (N > kMaxViewsPerLaunch) return for_view_slices(N, [&](int64_t n0, int64_t n) {
+    return drtk_amd_composite_layers_backward(
+        dtype, advance(grad_img, n0 * C * H * W, es), advance(grad_transmittance, n0 * H * W, es),
+        advance(color, n0 * color_strides[0], es), color_strides, advance(alpha, n0 * alpha_strides[0], es), alpha_strides,
+        advance_typed(index_img, n0 * K * H * W), advance(background, n0 * background_sN, es), background_sN, n, K, C, H, W,
+        advance(grad_color, grad_color ? n0 * grad_color_strides[0] : 0, es), grad_color_strides,
+        advance(grad_alpha, grad_alpha ? n0 * grad_alpha_strides[0] : 0, es), grad_alpha_strides,
+        advance(grad_background, n0 * C * H * W, es), stream);
+  });
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    auto a = composite_inputs<T>(color, color_strides, alpha, alpha_strides, index_img, background, background_sN, C, H * W);
+    a.g_img = static_cast<const T*>(grad_img), a.g_T = static_cast<const T*>(grad_transmittance);
+    a.g_color = static_cast<T*>(grad_color), a.g_alpha = static_cast<T*>(grad_alpha), a.g_bg = static_cast<T*>(grad_background);
+    if (grad_color) a.gc_sN = grad_color_strides[0], a.gc_sK = grad_color_strides[1], a.gc_sC = grad_color_strides[2];
+    if (grad_alpha) a.ga_sN = grad_alpha_strides[0], a.ga_sK = grad_alpha_strides[1];
+    composite_launch<T, true>(a, static_cast<int>(K), N, W, static_cast<hipStream_t>(stream));
+    DRTK_RETURN_IF_LAUNCH_FAILED();
+    return DRTK_OK;
+  });
 }

@@ -1321,7 +1321,7 @@ int edge_grad_backward_fused_impl(
 // ---------------------------------------------------------------------------------------------
 // the two planes of pair terms (gdx, gdy); never an empty allocation
 int edge_workspace_bytes(drtk_dtype_t dtype, int64_t N, int64_t H, int64_t W, size_t* bytes) {
-  if (!bytes || N < 0 || H < 0 || W < 0 || (dtype != DRTK_F32 && dtype != DRTK_F64)) return DRTK_ERR_INVALID_ARGUMENT;
+  if (!bytes || N < 0 || H < 0 || W < 0 || !valid_dtype(dtype)) return DRTK_ERR_INVALID_ARGUMENT;
   const size_t b = size_t(2) * N * H * W * dtype_size(dtype);
   *bytes = b > 0 ? b : 16;
   return DRTK_OK;
@@ -1335,9 +1335,7 @@ int check_edge_args(
     bool fused, drtk_dtype_t dtype, const void* v_pix, const void* img, const int32_t* index_img, const int32_t* vi,
     const void* bary_img, const void* grad_output, int64_t N, int64_t V, int64_t C, int64_t F, int64_t vi_sN, int64_t H,
     int64_t W, const void* out, const void* workspace, size_t workspace_bytes) {
-  if (N < 0 || V < 0 || C < 0 || F < 0 || H < 0 || W < 0 ||
-      (vi_sN != 0 && vi_sN != F * 3) || H * W >= (int64_t(1) << 31) || (dtype != DRTK_F32 && dtype != DRTK_F64))
-    return DRTK_ERR_INVALID_ARGUMENT;
+  if (bad_image(N, H, W) || V < 0 || C < 0 || F < 0 || bad_view_stride(vi_sN, F * 3) || !valid_dtype(dtype)) return DRTK_ERR_INVALID_ARGUMENT;
   if (!aligned_to(workspace, 16)) return DRTK_ERR_INVALID_ARGUMENT; // include/drtk_amd.h, alignment
   size_t need = 0;
   if (edge_workspace_bytes(dtype, N, H, W, &need) != DRTK_OK) return DRTK_ERR_INVALID_ARGUMENT;
@@ -1373,22 +1371,19 @@ extern "C" int drtk_amd_edge_grad_backward(
     size_t workspace_bytes, drtk_stream_t stream) {
   const int ok = check_edge_args(false, dtype, v_pix, img, index_img, vi, nullptr, grad_output, N, V, C, F, vi_sN, H, W, grad_v_pix_img, workspace, workspace_bytes);
   if (ok != DRTK_OK) return ok;
-  {
-    const size_t es = dtype_size(dtype); // (every slice reuses the front of the workspace: stream order)
-    DRTK_FOR_VIEW_SLICES(N, n0, n, drtk_amd_edge_grad_backward(
+  const size_t es = dtype_size(dtype);
+  if (N > kMaxViewsPerLaunch) return for_view_slices(N, [&](int64_t n0, int64_t n) { // (every slice reuses the front of the workspace: stream order)
+    return drtk_amd_edge_grad_backward(
         dtype, advance(v_pix, n0 * V * 3, es), advance(img, n0 * C * H * W, es), advance_typed(index_img, n0 * H * W),
         advance_typed(vi, n0 * vi_sN), advance(grad_output, n0 * C * H * W, es), n, V, C, F, vi_sN, H, W, max_dp_dr,
-        advance(grad_v_pix_img, n0 * 3 * H * W, es), workspace, workspace_bytes, stream))
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (dtype) {
-    case DRTK_F32:
-      return edge_grad_backward_impl<float>(static_cast<const float*>(v_pix), static_cast<const float*>(img), index_img, vi, static_cast<const float*>(grad_output), N, V, C, vi_sN, H, W, max_dp_dr, static_cast<float*>(grad_v_pix_img), workspace, s);
-    case DRTK_F64:
-      return edge_grad_backward_impl<double>(static_cast<const double*>(v_pix), static_cast<const double*>(img), index_img, vi, static_cast<const double*>(grad_output), N, V, C, vi_sN, H, W, max_dp_dr, static_cast<double*>(grad_v_pix_img), workspace, s);
-    default:
-      return DRTK_ERR_INVALID_ARGUMENT;
-  }
+        advance(grad_v_pix_img, n0 * 3 * H * W, es), workspace, workspace_bytes, stream);
+  });
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return edge_grad_backward_impl<T>(
+        static_cast<const T*>(v_pix), static_cast<const T*>(img), index_img, vi, static_cast<const T*>(grad_output), N, V, C, vi_sN, H, W,
+        max_dp_dr, static_cast<T*>(grad_v_pix_img), workspace, static_cast<hipStream_t>(stream));
+  });
 }
 
 extern "C" int drtk_amd_edge_grad_backward_fused(
@@ -1398,20 +1393,18 @@ extern "C" int drtk_amd_edge_grad_backward_fused(
     void* workspace, size_t workspace_bytes, drtk_stream_t stream) {
   const int ok = check_edge_args(true, dtype, v_pix, img, index_img, vi, bary_img, grad_output, N, V, C, F, vi_sN, H, W, grad_v_pix, workspace, workspace_bytes);
   if (ok != DRTK_OK) return ok;
-  {
-    const size_t es = dtype_size(dtype);
-    DRTK_FOR_VIEW_SLICES(N, n0, n, drtk_amd_edge_grad_backward_fused(
+  const size_t es = dtype_size(dtype);
+  if (N > kMaxViewsPerLaunch) return for_view_slices(N, [&](int64_t n0, int64_t n) {
+    return drtk_amd_edge_grad_backward_fused(
         dtype, advance(v_pix, n0 * V * 3, es), advance(img, n0 * C * H * W, es), advance_typed(index_img, n0 * H * W),
         advance_typed(vi, n0 * vi_sN), advance(bary_img, n0 * 3 * H * W, es), advance(grad_output, n0 * C * H * W, es), n, V, C, F,
-        vi_sN, H, W, max_dp_dr, advance(grad_v_pix, n0 * V * 3, es), workspace, workspace_bytes, stream))
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (dtype) {
-    case DRTK_F32:
-      return edge_grad_backward_fused_impl<float>(static_cast<const float*>(v_pix), static_cast<const float*>(img), index_img, vi, static_cast<const float*>(bary_img), static_cast<const float*>(grad_output), N, V, C, F, vi_sN, H, W, max_dp_dr, static_cast<float*>(grad_v_pix), workspace, s);
-    case DRTK_F64:
-      return edge_grad_backward_fused_impl<double>(static_cast<const double*>(v_pix), static_cast<const double*>(img), index_img, vi, static_cast<const double*>(bary_img), static_cast<const double*>(grad_output), N, V, C, F, vi_sN, H, W, max_dp_dr, static_cast<double*>(grad_v_pix), workspace, s);
-    default:
-      return DRTK_ERR_INVALID_ARGUMENT;
-  }
+        vi_sN, H, W, max_dp_dr, advance(grad_v_pix, n0 * V * 3, es), workspace, workspace_bytes, stream);
+  });
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return edge_grad_backward_fused_impl<T>(
+        static_cast<const T*>(v_pix), static_cast<const T*>(img), index_img, vi, static_cast<const T*>(bary_img),
+        static_cast<const T*>(grad_output), N, V, C, F, vi_sN, H, W, max_dp_dr, static_cast<T*>(grad_v_pix), workspace,
+        static_cast<hipStream_t>(stream));
+  });
 }

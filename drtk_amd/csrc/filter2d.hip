@@ -244,7 +244,7 @@ int f2d_axis(int64_t in, int64_t k, int64_t up, int64_t down, bool backward, int
 int f2d_validate(
     drtk_dtype_t dtype, int64_t planes, int64_t H, int64_t W, int64_t k, int64_t up, int64_t down, bool reflect, bool backward,
     int64_t* lead, int64_t* OH, int64_t* OW) {
-  if (dtype != DRTK_F32 && dtype != DRTK_F64 && dtype != DRTK_F16) return DRTK_ERR_INVALID_ARGUMENT;
+  if (!valid_dtype(dtype) && dtype != DRTK_F16) return DRTK_ERR_INVALID_ARGUMENT; // half: this operator only
   if (planes < 0) return DRTK_ERR_INVALID_ARGUMENT;
   int64_t total = 0;
   if (f2d_axis(H, k, up, down, backward, lead, &total, OH) != DRTK_OK) return DRTK_ERR_INVALID_ARGUMENT;
@@ -367,7 +367,9 @@ extern "C" int drtk_amd_filter2d(
   a.k = static_cast<int>(k), a.up = static_cast<int>(up), a.down = static_cast<int>(down), a.lead = static_cast<int>(lead);
   a.reflect = reflect != 0, a.reversed = backward == 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == DRTK_F32) return f2d_dispatch<float>(x, f, y, planes, a, force_generic != 0, s);
-  if (dtype == DRTK_F64) return f2d_dispatch<double>(x, f, y, planes, a, force_generic != 0, s);
-  return f2d_dispatch<half_t>(x, f, y, planes, a, force_generic != 0, s);
+  if (dtype == DRTK_F16) return f2d_dispatch<half_t>(x, f, y, planes, a, force_generic != 0, s);
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return f2d_dispatch<T>(x, f, y, planes, a, force_generic != 0, s);
+  });
 }

@@ -445,6 +445,7 @@ int vertex_gather_impl(const void* src, int64_t src_sN, int per_corner, int64_t 
   return DRTK_OK;
 }
 
+// (no image here, so no bad_image(): the limits are 32-bit vertex and corner indices and kMaxLanes, one lane per face or vertex)
 bool bad_sizes(int64_t N, int64_t V, int64_t F) {
   return N < 0 || V < 0 || F < 0 || V >= (int64_t(1) << 31) || F >= (int64_t(1) << 31) / 3 ||
          (N > 0 && (F > kMaxLanes / N || V > kMaxLanes / N));
@@ -455,34 +456,21 @@ bool bad_sizes(int64_t N, int64_t V, int64_t F) {
 
 using namespace drtk_amd;
 
-#define DRTK_GEOM_DISPATCH(dtype, CALL_T)         \
-  switch (dtype) {                                \
-    case DRTK_F32: {                              \
-      using T = float;                            \
-      return CALL_T;                              \
-    }                                             \
-    case DRTK_F64: {                              \
-      using T = double;                           \
-      return CALL_T;                              \
-    }                                             \
-    default:                                      \
-      return DRTK_ERR_INVALID_ARGUMENT;           \
-  }
-
 extern "C" int drtk_amd_geometry_face_forward(
     drtk_dtype_t dtype, const void* v, int64_t v_sN, const int32_t* vi, int64_t vi_sN, const void* vt, int64_t vt_sN,
     const int32_t* vti, int64_t N, int64_t V, int64_t T_, int64_t F, void* normals, void* areas, void* edges,
     void* dpdt, void* dpdt_u, void* v012, drtk_stream_t stream) {
-  if (dtype != DRTK_F32 && dtype != DRTK_F64) return DRTK_ERR_INVALID_ARGUMENT;
+  if (!valid_dtype(dtype)) return DRTK_ERR_INVALID_ARGUMENT;
   if (bad_sizes(N, V, F) || T_ < 0 || T_ >= (int64_t(1) << 31)) return DRTK_ERR_INVALID_ARGUMENT;
-  if ((v_sN != 0 && v_sN != V * 3) || (vi_sN != 0 && vi_sN != F * 3) || (vt_sN != 0 && vt_sN != T_ * 2))
-    return DRTK_ERR_INVALID_ARGUMENT;
+  if (bad_view_stride(v_sN, V * 3) || bad_view_stride(vi_sN, F * 3) || bad_view_stride(vt_sN, T_ * 2)) return DRTK_ERR_INVALID_ARGUMENT;
   const bool uv = dpdt || dpdt_u;
   if (N * F == 0) return DRTK_OK; // (outputs without elements may be NULL)
   if (!normals && !areas && !edges && !uv && !v012) return DRTK_ERR_INVALID_ARGUMENT;
   if (!v || !vi || V == 0 || (uv && (!vt || !vti || T_ == 0))) return DRTK_ERR_INVALID_ARGUMENT;
-  DRTK_GEOM_DISPATCH(dtype, face_forward_impl<T>(v, v_sN, vi, vi_sN, vt, vt_sN, vti, N, F, normals, areas, edges, dpdt,
-                                                 dpdt_u, v012, static_cast<hipStream_t>(stream)))
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return face_forward_impl<T>(v, v_sN, vi, vi_sN, vt, vt_sN, vti, N, F, normals, areas, edges, dpdt, dpdt_u, v012, static_cast<hipStream_t>(stream));
+  });
 }
 
 extern "C" int drtk_amd_geometry_face_backward(
@@ -490,36 +478,40 @@ extern "C" int drtk_amd_geometry_face_backward(
     const int32_t* vti, int64_t N, int64_t V, int64_t T_, int64_t F, const void* grad_vert, const void* vert_sums,
     const void* grad_normals, const void* grad_areas, const void* grad_edges, const void* grad_dpdt,
     const void* grad_v012, void* pos_rows, void* uv_rows, drtk_stream_t stream) {
-  if (dtype != DRTK_F32 && dtype != DRTK_F64) return DRTK_ERR_INVALID_ARGUMENT;
+  if (!valid_dtype(dtype)) return DRTK_ERR_INVALID_ARGUMENT;
   if (bad_sizes(N, V, F) || T_ < 0 || T_ >= (int64_t(1) << 31)) return DRTK_ERR_INVALID_ARGUMENT;
-  if ((v_sN != 0 && v_sN != V * 3) || (vi_sN != 0 && vi_sN != F * 3) || (vt_sN != 0 && vt_sN != T_ * 2))
-    return DRTK_ERR_INVALID_ARGUMENT;
+  if (bad_view_stride(v_sN, V * 3) || bad_view_stride(vi_sN, F * 3) || bad_view_stride(vt_sN, T_ * 2)) return DRTK_ERR_INVALID_ARGUMENT;
   const bool dp = vt != nullptr;
   if (dp ? (grad_normals || grad_areas || grad_edges || !uv_rows || !vti) : (grad_dpdt || grad_v012 || uv_rows))
     return DRTK_ERR_INVALID_ARGUMENT;
   if (vert_sums && !grad_vert) return DRTK_ERR_INVALID_ARGUMENT;
   if (N * F == 0) return DRTK_OK;
   if (!v || !vi || !pos_rows || V == 0 || (dp && T_ == 0)) return DRTK_ERR_INVALID_ARGUMENT;
-  DRTK_GEOM_DISPATCH(dtype, face_backward_impl<T>(v, v_sN, vi, vi_sN, vt, vt_sN, vti, N, V, F, grad_vert, vert_sums,
-                                                  grad_normals, grad_areas, grad_edges, grad_dpdt, grad_v012, pos_rows,
-                                                  uv_rows, static_cast<hipStream_t>(stream)))
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return face_backward_impl<T>(
+        v, v_sN, vi, vi_sN, vt, vt_sN, vti, N, V, F, grad_vert, vert_sums, grad_normals, grad_areas, grad_edges, grad_dpdt, grad_v012,
+        pos_rows, uv_rows, static_cast<hipStream_t>(stream));
+  });
 }
 
 extern "C" int drtk_amd_geometry_face_gather(
     drtk_dtype_t dtype, const void* grad_vert, const void* vert_sums, const int32_t* vi, int64_t vi_sN, int64_t N,
     int64_t V, int64_t F, int64_t A, void* out, drtk_stream_t stream) {
-  if (dtype != DRTK_F32 && dtype != DRTK_F64) return DRTK_ERR_INVALID_ARGUMENT;
-  if (bad_sizes(N, V, F) || A < 1 || (vert_sums && A != 3) || (vi_sN != 0 && vi_sN != F * 3))
+  if (!valid_dtype(dtype)) return DRTK_ERR_INVALID_ARGUMENT;
+  if (bad_sizes(N, V, F) || A < 1 || (vert_sums && A != 3) || bad_view_stride(vi_sN, F * 3))
     return DRTK_ERR_INVALID_ARGUMENT;
   if (N * F == 0) return DRTK_OK;
   if (!grad_vert || !vi || !out || V == 0) return DRTK_ERR_INVALID_ARGUMENT;
-  DRTK_GEOM_DISPATCH(dtype, face_gather_impl<T>(grad_vert, vert_sums, vi, vi_sN, N, V, F, A, out,
-                                                static_cast<hipStream_t>(stream)))
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return face_gather_impl<T>(grad_vert, vert_sums, vi, vi_sN, N, V, F, A, out, static_cast<hipStream_t>(stream));
+  });
 }
 
 extern "C" int drtk_amd_geometry_vertex_gather_workspace_bytes(
     drtk_dtype_t dtype, int64_t N, int64_t B, int64_t num_chunks, int64_t A, size_t* bytes) {
-  if ((dtype != DRTK_F32 && dtype != DRTK_F64) || !bytes || N < 0 || num_chunks < 0 || A < 1 || (B != 1 && B != N))
+  if (!valid_dtype(dtype) || !bytes || N < 0 || num_chunks < 0 || A < 1 || (B != 1 && B != N))
     return DRTK_ERR_INVALID_ARGUMENT;
   *bytes = size_t((B == 1 ? N : 1) * num_chunks * A) * dtype_size(dtype);
   return DRTK_OK;
@@ -530,7 +522,7 @@ extern "C" int drtk_amd_geometry_vertex_gather(
     const int32_t* entries, const int32_t* chunk_ptr, const int32_t* chunk_begin, const int32_t* chunk_row,
     int64_t num_chunks, int64_t B, int64_t N, int64_t V, int64_t F, int normalize, void* out, void* vert_sums,
     void* workspace, size_t workspace_bytes, drtk_stream_t stream) {
-  if (dtype != DRTK_F32 && dtype != DRTK_F64) return DRTK_ERR_INVALID_ARGUMENT;
+  if (!valid_dtype(dtype)) return DRTK_ERR_INVALID_ARGUMENT;
   if (bad_sizes(N, V, F) || A < 1 || num_chunks < 0 || (normalize && A != 3) || (vert_sums && !normalize))
     return DRTK_ERR_INVALID_ARGUMENT;
   if ((B != 1 && B != N) || (per_corner != 0 && per_corner != 1) || src_sN != F * A * (per_corner ? 3 : 1))
@@ -544,7 +536,10 @@ extern "C" int drtk_amd_geometry_vertex_gather(
     drtk_amd_geometry_vertex_gather_workspace_bytes(dtype, N, B, num_chunks, A, &need);
     if (!workspace || workspace_bytes < need) return DRTK_ERR_WORKSPACE_TOO_SMALL;
   }
-  DRTK_GEOM_DISPATCH(dtype, vertex_gather_impl<T>(src, src_sN, per_corner, A, crow, entries, chunk_ptr, chunk_begin,
-                                                  chunk_row, num_chunks, B, N, V, out, vert_sums, normalize, workspace,
-                                                  static_cast<hipStream_t>(stream)))
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return vertex_gather_impl<T>(
+        src, src_sN, per_corner, A, crow, entries, chunk_ptr, chunk_begin, chunk_row, num_chunks, B, N, V, out, vert_sums, normalize,
+        workspace, static_cast<hipStream_t>(stream));
+  });
 }

@@ -303,10 +303,11 @@ __global__ __launch_bounds__(kBlock) void grid_scatter_backward_kernel(
 
 int gs_validate(drtk_dtype_t dtype, int64_t N, int64_t C, int64_t H, int64_t W, int64_t OH, int64_t OW, int padding_mode, int interpolation_mode) {
   constexpr int64_t kLimit = int64_t(1) << 31;
-  if (N < 0 || C < 0 || H < 0 || W < 0 || H >= kLimit || W >= kLimit || H * W >= kLimit || C >= (1 << 20)) return DRTK_ERR_INVALID_ARGUMENT;
+  // (not bad_image() alone: H and W are bounded one by one, too -- an empty input of 2^31 rows is invalid here)
+  if (H >= kLimit || W >= kLimit || bad_image(N, H, W) || C < 0 || C >= (1 << 20)) return DRTK_ERR_INVALID_ARGUMENT;
   if (OH <= 0 || OW <= 0 || OH >= kLimit || OW >= kLimit || OH * OW >= kLimit) return DRTK_ERR_INVALID_ARGUMENT;
   if (padding_mode < 0 || padding_mode > 2 || (interpolation_mode != 0 && interpolation_mode != 2)) return DRTK_ERR_INVALID_ARGUMENT;
-  if (dtype != DRTK_F32 && dtype != DRTK_F64) return DRTK_ERR_INVALID_ARGUMENT;
+  if (!valid_dtype(dtype)) return DRTK_ERR_INVALID_ARGUMENT;
   return DRTK_OK;
 }
 
@@ -314,17 +315,6 @@ int gs_validate(drtk_dtype_t dtype, int64_t N, int64_t C, int64_t H, int64_t W, 
 } // namespace drtk_amd
 
 using namespace drtk_amd;
-
-#define GS_DISPATCH(LAUNCH)                                                                        \
-  do {                                                                                             \
-    if (dtype == DRTK_F32) {                                                                       \
-      if (interpolation_mode == 0) { GS_DISPATCH_PAD(LAUNCH, float, 0); } else { GS_DISPATCH_PAD(LAUNCH, float, 2); } \
-    } else {                                                                                       \
-      if (interpolation_mode == 0) { GS_DISPATCH_PAD(LAUNCH, double, 0); } else { GS_DISPATCH_PAD(LAUNCH, double, 2); } \
-    }                                                                                              \
-  } while (0)
-#define GS_DISPATCH_PAD(LAUNCH, T, MODE) \
-  if (padding_mode == 0) LAUNCH(T, MODE, 0); else if (padding_mode == 1) LAUNCH(T, MODE, 1); else LAUNCH(T, MODE, 2)
 
 extern "C" int drtk_amd_grid_scatter_2d(
     drtk_dtype_t dtype, const void* input, const void* grid, const int64_t* grid_layout, int64_t N, int64_t C, int64_t H,
@@ -339,26 +329,32 @@ extern "C" int drtk_amd_grid_scatter_2d(
   if (count > 0 && C > 0 && (!input || !grid)) return DRTK_ERR_INVALID_ARGUMENT;
   GridLayout gl;
   if (make_grid_layout(gl, grid_layout, grid, H, W, es) != DRTK_OK) return DRTK_ERR_INVALID_ARGUMENT;
-  {
+  if (N > kMaxViewsPerLaunch) return for_view_slices(N, [&](int64_t n0, int64_t n) {
     const int64_t layout[3] = {gl.sN, gl.sP, gl.sC};
-    DRTK_FOR_VIEW_SLICES(N, n0, n, drtk_amd_grid_scatter_2d(
+    return drtk_amd_grid_scatter_2d(
         dtype, advance(input, n0 * C * H * W, es), advance(grid, n0 * gl.sN, es), layout, n, C, H, W, OH, OW, padding_mode,
-        interpolation_mode, align_corners, advance(out, n0 * C * OH * OW, es), route_counts, stream))
-  }
+        interpolation_mode, align_corners, advance(out, n0 * C * OH * OW, es), route_counts, stream);
+  });
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (out_elems > 0 && fill_bytes_async(out, 0, es * size_t(out_elems), s) != DRTK_OK) return DRTK_ERR_LAUNCH;
   if (count == 0 || C == 0) return DRTK_OK;
   const int tiles_x = static_cast<int>(ceil_div(W, kGsTileW)), tiles_y = static_cast<int>(ceil_div(H, kGsTileH));
   const dim3 grid_dim(static_cast<unsigned>(int64_t(tiles_x) * tiles_y), static_cast<unsigned>(N));
-#define GS_FWD(T, MODE, PAD)                                                                                              \
-  DRTK_LAUNCH(                                                                                                            \
-      (grid_scatter_forward_kernel<T, MODE, PAD>), grid_dim, dim3(kBlock), 0, s, static_cast<const T*>(input),            \
-      static_cast<const T*>(grid), gl, (int)C, (int)H, (int)W, (int)OH, (int)OW, tiles_x, align_corners != 0,             \
-      static_cast<T*>(out), route_counts, xcd_strip(tiles_x))
-  GS_DISPATCH(GS_FWD);
-#undef GS_FWD
-  DRTK_RETURN_IF_LAUNCH_FAILED();
-  return DRTK_OK;
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    with_constant<0, 1>(interpolation_mode / 2, [&](auto bicubic) {
+      with_constant<0, 2>(padding_mode, [&](auto pad) {
+        constexpr int MODE = 2 * decltype(bicubic)::value, PAD = decltype(pad)::value;
+        static const std::string name = instance_name<MODE, PAD>("grid_scatter_forward_kernel");
+        launch_as(
+            name, grid_scatter_forward_kernel<T, MODE, PAD>, grid_dim, kBlock, 0, s, static_cast<const T*>(input),
+            static_cast<const T*>(grid), gl, (int)C, (int)H, (int)W, (int)OH, (int)OW, tiles_x, align_corners != 0,
+            static_cast<T*>(out), route_counts, xcd_strip(tiles_x));
+      });
+    });
+    DRTK_RETURN_IF_LAUNCH_FAILED();
+    return DRTK_OK;
+  });
 }
 
 extern "C" int drtk_amd_grid_scatter_2d_backward(
@@ -376,23 +372,29 @@ extern "C" int drtk_amd_grid_scatter_2d_backward(
   GridLayout gl, ggl;
   if (make_grid_layout(gl, grid_layout, grid, H, W, es) != DRTK_OK || make_grid_layout(ggl, grad_grid_layout, grad_grid, H, W, es) != DRTK_OK)
     return DRTK_ERR_INVALID_ARGUMENT;
-  {
+  if (N > kMaxViewsPerLaunch) return for_view_slices(N, [&](int64_t n0, int64_t n) {
     const int64_t layout[3] = {gl.sN, gl.sP, gl.sC}, glayout[3] = {ggl.sN, ggl.sP, ggl.sC};
-    DRTK_FOR_VIEW_SLICES(N, n0, n, drtk_amd_grid_scatter_2d_backward(
+    return drtk_amd_grid_scatter_2d_backward(
         dtype, advance(grad_out, n0 * C * OH * OW, es), advance(input, n0 * C * H * W, es), advance(grid, n0 * gl.sN, es), layout, n,
         C, H, W, OH, OW, padding_mode, interpolation_mode, align_corners, advance(grad_input, n0 * C * H * W, es),
-        advance(grad_grid, n0 * ggl.sN, es), glayout, stream))
-  }
+        advance(grad_grid, n0 * ggl.sN, es), glayout, stream);
+  });
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int64_t HW = H * W;
   const dim3 grid_dim(static_cast<unsigned>(ceil_div(HW, kBlock)), static_cast<unsigned>(N));
-#define GS_BWD(T, MODE, PAD)                                                                                              \
-  DRTK_LAUNCH(                                                                                                            \
-      (grid_scatter_backward_kernel<T, MODE, PAD>), grid_dim, dim3(kBlock), 0, s, static_cast<const T*>(grad_out),        \
-      static_cast<const T*>(input), static_cast<const T*>(grid), gl, (int)C, HW, (int)OH, (int)OW, align_corners != 0,    \
-      static_cast<T*>(grad_input), static_cast<T*>(grad_grid), ggl, xcd_strip(ceil_div(16 * W, kBlock)))
-  GS_DISPATCH(GS_BWD);
-#undef GS_BWD
-  DRTK_RETURN_IF_LAUNCH_FAILED();
-  return DRTK_OK;
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    with_constant<0, 1>(interpolation_mode / 2, [&](auto bicubic) {
+      with_constant<0, 2>(padding_mode, [&](auto pad) {
+        constexpr int MODE = 2 * decltype(bicubic)::value, PAD = decltype(pad)::value;
+        static const std::string name = instance_name<MODE, PAD>("grid_scatter_backward_kernel");
+        launch_as(
+            name, grid_scatter_backward_kernel<T, MODE, PAD>, grid_dim, kBlock, 0, s, static_cast<const T*>(grad_out),
+            static_cast<const T*>(input), static_cast<const T*>(grid), gl, (int)C, HW, (int)OH, (int)OW, align_corners != 0,
+            static_cast<T*>(grad_input), static_cast<T*>(grad_grid), ggl, xcd_strip(ceil_div(16 * W, kBlock)));
+      });
+    });
+    DRTK_RETURN_IF_LAUNCH_FAILED();
+    return DRTK_OK;
+  });
 }

@@ -545,7 +545,7 @@ int il_backward(
 int il_validate(
     drtk_dtype_t dtype, int64_t N, int64_t C, int64_t H, int64_t W, int window_size, double sigma, double data_range, int valid, int mode,
     int weight_kind, double l1_weight, double ssim_weight, IlShape* s, double* g) {
-  if (dtype != DRTK_F32 && dtype != DRTK_F64) return DRTK_ERR_INVALID_ARGUMENT;
+  if (!valid_dtype(dtype)) return DRTK_ERR_INVALID_ARGUMENT;
   if (mode != IL_MAP && mode != IL_SSIM && mode != IL_PHOTOMETRIC) return DRTK_ERR_INVALID_ARGUMENT;
   if (weight_kind != IL_W_NONE && weight_kind != IL_W_BOOL && weight_kind != IL_W_REAL) return DRTK_ERR_INVALID_ARGUMENT;
   if (mode == IL_MAP && weight_kind != IL_W_NONE) return DRTK_ERR_INVALID_ARGUMENT;
@@ -585,14 +585,12 @@ extern "C" int drtk_amd_image_loss_forward(
     if (!scalars || !workspace) return DRTK_ERR_INVALID_ARGUMENT;
     if (workspace_bytes < size_t(s.blocks) * kIlSums * sizeof(double)) return DRTK_ERR_WORKSPACE_TOO_SMALL;
   }
-  hipStream_t hs = static_cast<hipStream_t>(stream);
-  if (dtype == DRTK_F32)
-    return il_forward<float>(
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return il_forward<T>(
         img, img_strides, target, target_strides, weight, weight_kind, weight_strides, N, C, H, W, window_size, g, s, data_range, mode,
-        l1_weight, ssim_weight, out, maps, scalars, workspace, hs);
-  return il_forward<double>(
-      img, img_strides, target, target_strides, weight, weight_kind, weight_strides, N, C, H, W, window_size, g, s, data_range, mode,
-      l1_weight, ssim_weight, out, maps, scalars, workspace, hs);
+        l1_weight, ssim_weight, out, maps, scalars, workspace, static_cast<hipStream_t>(stream));
+  });
 }
 
 extern "C" int drtk_amd_image_loss_backward(
@@ -608,12 +606,10 @@ extern "C" int drtk_amd_image_loss_backward(
     return DRTK_ERR_INVALID_ARGUMENT;
   if (weight_kind != IL_W_NONE && (!weight || !il_strides_ok(weight_strides, 2))) return DRTK_ERR_INVALID_ARGUMENT;
   if (mode != IL_MAP && !scalars) return DRTK_ERR_INVALID_ARGUMENT;
-  hipStream_t hs = static_cast<hipStream_t>(stream);
-  if (dtype == DRTK_F32)
-    return il_backward<float>(
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return il_backward<T>(
         img, img_strides, target, target_strides, weight, weight_kind, weight_strides, N, C, H, W, window_size, g, s, data_range, mode,
-        l1_weight, ssim_weight, maps, grad_out, scalars, grad_img, hs);
-  return il_backward<double>(
-      img, img_strides, target, target_strides, weight, weight_kind, weight_strides, N, C, H, W, window_size, g, s, data_range, mode,
-      l1_weight, ssim_weight, maps, grad_out, scalars, grad_img, hs);
+        l1_weight, ssim_weight, maps, grad_out, scalars, grad_img, static_cast<hipStream_t>(stream));
+  });
 }

@@ -175,8 +175,23 @@ __global__ __launch_bounds__(kBlock) void normal_matrix_values_backward_kernel(
   gp[0] = o0, gp[HW] = o1, gp[2 * HW] = o2;
 }
 
-bool bad(int64_t N, int64_t F, int64_t H, int64_t W) {
-  return N < 0 || F < 0 || H < 0 || W < 0 || H * W >= (int64_t(1) << 31);
+// The argument check of the CSR pair, complete before either writes anything (tests/test_interp_matrix_args_host.py pins every
+// status of the four entries).  `row_pointers`: every pointer a row reads or writes is there -- the forward's six, the backward's
+// four inputs -- required as soon as there is a row.  `bary_grad`: whether the backward's output is there, which it clears -- so
+// requires -- wherever there is a pixel, rows or not (the forward says true).  Rows address pixels of any view: no slicing, any N.
+// (`vi` is required with F = 0 too: the kernels are not told F.)
+int check_matrix_args(drtk_dtype_t dtype, int64_t R, int64_t N, int64_t F, int64_t vi_sN, int64_t H, int64_t W, bool row_pointers, bool bary_grad) {
+  if (!valid_dtype(dtype) || bad_image(N, H, W) || F < 0 || R < 0 || bad_view_stride(vi_sN, F * 3)) return DRTK_ERR_INVALID_ARGUMENT;
+  if ((N * H * W > 0 && !bary_grad) || (R > 0 && !row_pointers)) return DRTK_ERR_INVALID_ARGUMENT;
+  return DRTK_OK;
+}
+
+// ... and of the normal-matrix pair.  Its kernels take the view from blockIdx.y and the forward sums all views into ONE values
+// array: no slicing here, kMaxViewsPerLaunch views at the most.
+int check_normal_matrix_args(drtk_dtype_t dtype, int64_t N, int64_t F, int64_t pair_sN, int64_t H, int64_t W, int64_t nnz) {
+  if (!valid_dtype(dtype) || bad_image(N, H, W) || F < 0 || N > kMaxViewsPerLaunch || nnz < 0 || bad_view_stride(pair_sN, F * 9))
+    return DRTK_ERR_INVALID_ARGUMENT;
+  return DRTK_OK;
 }
 
 } // namespace
@@ -184,106 +199,85 @@ bool bad(int64_t N, int64_t F, int64_t H, int64_t W) {
 
 using namespace drtk_amd;
 
-#define DRTK_DISPATCH(dtype, CALL_F32, CALL_F64) \
-  switch (dtype) {                               \
-    case DRTK_F32: {                             \
-      using T = float;                           \
-      CALL_F32;                                  \
-      break;                                     \
-    }                                            \
-    case DRTK_F64: {                             \
-      using T = double;                          \
-      CALL_F64;                                  \
-      break;                                     \
-    }                                            \
-    default:                                     \
-      return DRTK_ERR_INVALID_ARGUMENT;          \
-  }
-
 extern "C" int drtk_amd_interpolation_matrix(
     drtk_dtype_t dtype, const int32_t* vi, const int32_t* index_img, const void* bary_img,
     const int64_t* row_pixels, int64_t R, int64_t N, int64_t F, int64_t vi_sN, int64_t H, int64_t W,
     int64_t* col_indices, void* values, drtk_stream_t stream) {
-  if (bad(N, F, H, W) || R < 0 || (vi_sN != 0 && vi_sN != F * 3)) return DRTK_ERR_INVALID_ARGUMENT;
-  if (R == 0) return DRTK_OK;
-  if (!vi || !index_img || !bary_img || !row_pixels || !col_indices || !values) return DRTK_ERR_INVALID_ARGUMENT;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 grid(static_cast<unsigned>(ceil_div(R, kBlock)));
-#define CALL DRTK_LAUNCH((interpolation_matrix_kernel<T>), grid, dim3(kBlock), 0, s, vi, index_img, static_cast<const T*>(bary_img), row_pixels, R, vi_sN, H * W, col_indices, static_cast<T*>(values))
-  DRTK_DISPATCH(dtype, CALL, CALL)
-#undef CALL
-  DRTK_RETURN_IF_LAUNCH_FAILED();
-  return DRTK_OK;
+  const int st = check_matrix_args(dtype, R, N, F, vi_sN, H, W, vi && index_img && bary_img && row_pixels && col_indices && values, true);
+  if (st != DRTK_OK || R == 0) return st;
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    const dim3 grid(static_cast<unsigned>(ceil_div(R, kBlock)));
+    DRTK_LAUNCH(
+        (interpolation_matrix_kernel<T>), grid, dim3(kBlock), 0, static_cast<hipStream_t>(stream), vi, index_img,
+        static_cast<const T*>(bary_img), row_pixels, R, vi_sN, H * W, col_indices, static_cast<T*>(values));
+    DRTK_RETURN_IF_LAUNCH_FAILED();
+    return DRTK_OK;
+  });
 }
 
 extern "C" int drtk_amd_interpolation_matrix_backward(
     drtk_dtype_t dtype, const void* grad_values, const int32_t* vi, const int32_t* index_img,
     const int64_t* row_pixels, int64_t R, int64_t N, int64_t F, int64_t vi_sN, int64_t H, int64_t W,
     void* bary_grad, drtk_stream_t stream) {
-  if (bad(N, F, H, W) || R < 0 || (vi_sN != 0 && vi_sN != F * 3)) return DRTK_ERR_INVALID_ARGUMENT;
-  if (dtype != DRTK_F32 && dtype != DRTK_F64) return DRTK_ERR_INVALID_ARGUMENT;
+  const int st = check_matrix_args(dtype, R, N, F, vi_sN, H, W, grad_values && vi && index_img && row_pixels, bary_grad != nullptr);
+  if (st != DRTK_OK) return st;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const size_t es = dtype == DRTK_F32 ? 4 : 8;
-  if (N * H * W > 0) {
-    if (!bary_grad) return DRTK_ERR_INVALID_ARGUMENT;
-    if (fill_bytes_async(bary_grad, 0, es * 3 * N * H * W, s) != DRTK_OK) return DRTK_ERR_LAUNCH; // cpu :512
-  }
+  if (N * H * W > 0 && fill_bytes_async(bary_grad, 0, dtype_size(dtype) * 3 * N * H * W, s) != DRTK_OK) return DRTK_ERR_LAUNCH; // cpu :512
   if (R == 0) return DRTK_OK;
-  if (!grad_values || !vi || !index_img || !row_pixels) return DRTK_ERR_INVALID_ARGUMENT;
-  const dim3 grid(static_cast<unsigned>(ceil_div(R, kBlock)));
-#define CALL DRTK_LAUNCH((interpolation_matrix_backward_kernel<T>), grid, dim3(kBlock), 0, s, static_cast<const T*>(grad_values), vi, index_img, row_pixels, R, vi_sN, H * W, static_cast<T*>(bary_grad))
-  DRTK_DISPATCH(dtype, CALL, CALL)
-#undef CALL
-  DRTK_RETURN_IF_LAUNCH_FAILED();
-  return DRTK_OK;
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    const dim3 grid(static_cast<unsigned>(ceil_div(R, kBlock)));
+    DRTK_LAUNCH(
+        (interpolation_matrix_backward_kernel<T>), grid, dim3(kBlock), 0, s, static_cast<const T*>(grad_values), vi, index_img,
+        row_pixels, R, vi_sN, H * W, static_cast<T*>(bary_grad));
+    DRTK_RETURN_IF_LAUNCH_FAILED();
+    return DRTK_OK;
+  });
 }
 
 extern "C" int drtk_amd_interpolation_normal_matrix_values(
     drtk_dtype_t dtype, const int32_t* pair_indices, const int32_t* index_img, const void* bary_img,
     int64_t N, int64_t F, int64_t pair_sN, int64_t H, int64_t W, int64_t nnz, void* values,
     drtk_stream_t stream) {
-  // (the two normal-matrix kernels take the view from blockIdx.y and accumulate into ONE values array: no slicing here)
-  if (bad(N, F, H, W) || N > kMaxViewsPerLaunch || nnz < 0 || (pair_sN != 0 && pair_sN != F * 9)) return DRTK_ERR_INVALID_ARGUMENT;
-  if (dtype != DRTK_F32 && dtype != DRTK_F64) return DRTK_ERR_INVALID_ARGUMENT;
+  const int st = check_normal_matrix_args(dtype, N, F, pair_sN, H, W, nnz);
+  if (st != DRTK_OK) return st;
+  // `values` is cleared wherever it has an entry; the images are read only where there is a pixel to add to it
+  if (nnz > 0 && (!values || (N * H * W > 0 && (!pair_indices || !index_img || !bary_img)))) return DRTK_ERR_INVALID_ARGUMENT;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const size_t es = dtype == DRTK_F32 ? 4 : 8;
-  if (nnz > 0) {
-    if (!values) return DRTK_ERR_INVALID_ARGUMENT;
-    if (fill_bytes_async(values, 0, es * nnz, s) != DRTK_OK) return DRTK_ERR_LAUNCH; // cpu :586
-  }
+  if (nnz > 0 && fill_bytes_async(values, 0, dtype_size(dtype) * nnz, s) != DRTK_OK) return DRTK_ERR_LAUNCH; // cpu :586
   if (N * H * W == 0 || nnz == 0) return DRTK_OK;
-  if (!pair_indices || !index_img || !bary_img) return DRTK_ERR_INVALID_ARGUMENT;
-  const int tiles_x = static_cast<int>(ceil_div(W, kWave)), tiles_y = static_cast<int>(ceil_div(H, kTileRows));
-  const dim3 grid(static_cast<unsigned>(int64_t(tiles_x) * tiles_y), static_cast<unsigned>(N));
-#define CALL DRTK_LAUNCH((normal_matrix_values_kernel<T>), grid, dim3(kBlock), 0, s, pair_indices, index_img, static_cast<const T*>(bary_img), pair_sN, (int)H, (int)W, tiles_x, static_cast<T*>(values), xcd_strip(int64_t(tiles_x) * (16 / kTileRows)))
-  DRTK_DISPATCH(dtype, CALL, CALL)
-#undef CALL
-  DRTK_RETURN_IF_LAUNCH_FAILED();
-  return DRTK_OK;
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    const int tiles_x = static_cast<int>(ceil_div(W, kWave)), tiles_y = static_cast<int>(ceil_div(H, kTileRows));
+    const dim3 grid(static_cast<unsigned>(int64_t(tiles_x) * tiles_y), static_cast<unsigned>(N));
+    DRTK_LAUNCH(
+        (normal_matrix_values_kernel<T>), grid, dim3(kBlock), 0, s, pair_indices, index_img, static_cast<const T*>(bary_img), pair_sN,
+        (int)H, (int)W, tiles_x, static_cast<T*>(values), xcd_strip(int64_t(tiles_x) * (16 / kTileRows)));
+    DRTK_RETURN_IF_LAUNCH_FAILED();
+    return DRTK_OK;
+  });
 }
 
 extern "C" int drtk_amd_interpolation_normal_matrix_values_backward(
     drtk_dtype_t dtype, const void* grad_values, const int32_t* pair_indices, const int32_t* index_img,
     const void* bary_img, int64_t N, int64_t F, int64_t pair_sN, int64_t H, int64_t W, void* bary_grad,
     drtk_stream_t stream) {
-  if (bad(N, F, H, W) || N > kMaxViewsPerLaunch || (pair_sN != 0 && pair_sN != F * 9)) return DRTK_ERR_INVALID_ARGUMENT;
-  if (dtype != DRTK_F32 && dtype != DRTK_F64) return DRTK_ERR_INVALID_ARGUMENT;
-  if (N * H * W == 0) return DRTK_OK;
-  if (!bary_grad) return DRTK_ERR_INVALID_ARGUMENT;
+  const int st = check_normal_matrix_args(dtype, N, F, pair_sN, H, W, 0);
+  if (st != DRTK_OK || N * H * W == 0) return st;
+  // No faces: every pixel is background and its gradient is zero.  The pair table and grad_values are empty then and have no
+  // storage -- a null pointer is not a missing argument (same idiom as drtk_amd_interpolation_matrix_backward above: write
+  // the output, return when there is nothing to scatter).
+  if (!bary_grad || (F > 0 && (!grad_values || !pair_indices || !index_img || !bary_img))) return DRTK_ERR_INVALID_ARGUMENT;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (F == 0) {
-    // No faces: every pixel is background and its gradient is zero.  The pair table and grad_values are empty
-    // then and have no storage -- a null pointer is not a missing argument here (same idiom as
-    // drtk_amd_interpolation_matrix_backward above: write the output, return when there is nothing to scatter).
-    const size_t es = dtype == DRTK_F32 ? 4 : 8;
-    if (fill_bytes_async(bary_grad, 0, es * 3 * N * H * W, s) != DRTK_OK) return DRTK_ERR_LAUNCH;
+  if (F == 0) return fill_bytes_async(bary_grad, 0, dtype_size(dtype) * 3 * N * H * W, s) != DRTK_OK ? DRTK_ERR_LAUNCH : DRTK_OK;
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    const dim3 grid(static_cast<unsigned>(ceil_div(H * W, kBlock)), static_cast<unsigned>(N));
+    DRTK_LAUNCH(
+        (normal_matrix_values_backward_kernel<T>), grid, dim3(kBlock), 0, s, static_cast<const T*>(grad_values), pair_indices,
+        index_img, static_cast<const T*>(bary_img), pair_sN, H * W, static_cast<T*>(bary_grad));
+    DRTK_RETURN_IF_LAUNCH_FAILED();
     return DRTK_OK;
-  }
-  if (!grad_values || !pair_indices || !index_img || !bary_img) return DRTK_ERR_INVALID_ARGUMENT;
-  const dim3 grid(static_cast<unsigned>(ceil_div(H * W, kBlock)), static_cast<unsigned>(N));
-#define CALL DRTK_LAUNCH((normal_matrix_values_backward_kernel<T>), grid, dim3(kBlock), 0, s, static_cast<const T*>(grad_values), pair_indices, index_img, static_cast<const T*>(bary_img), pair_sN, H * W, static_cast<T*>(bary_grad))
-  DRTK_DISPATCH(dtype, CALL, CALL)
-#undef CALL
-  DRTK_RETURN_IF_LAUNCH_FAILED();
-  return DRTK_OK;
+  });
 }

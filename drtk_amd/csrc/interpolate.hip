@@ -1186,15 +1186,14 @@ int interpolate_backward_impl(
 
 // ---- argument checks shared by the entry points ------------------------------------------------------------------------------------
 bool bad_common(int64_t N, int64_t V, int64_t C, int64_t F, int64_t vi_sN, int64_t H, int64_t W) {
-  return N < 0 || V < 0 || C < 0 || F < 0 || H < 0 || W < 0 || C >= (1 << 20) ||
-      (vi_sN != 0 && vi_sN != F * 3) || H * W >= (int64_t(1) << 31);
+  return bad_image(N, H, W) || V < 0 || C < 0 || F < 0 || C >= (1 << 20) || bad_view_stride(vi_sN, F * 3);
 }
 // ... after the sizes, in this order: the per-pixel pointers (pixel_ptrs: the caller's are all there), the per-vertex ones, and
 // the dtype last
 bool bad_inputs(drtk_dtype_t dtype, const void* attrs, const int32_t* vi, bool pixel_ptrs, int64_t N, int64_t V, int64_t C, int64_t F, int64_t H, int64_t W) {
   if (N * H * W * C > 0 && !pixel_ptrs) return true;
   if ((N * V * C > 0 && !attrs) || (F > 0 && !vi)) return true;
-  return dtype != DRTK_F32 && dtype != DRTK_F64;
+  return !valid_dtype(dtype);
 }
 
 } // namespace
@@ -1209,13 +1208,17 @@ static int interpolate_entry(
   if (bad_common(N, V, C, F, vi_sN, H, W)) return DRTK_ERR_INVALID_ARGUMENT;
   if (bad_inputs(dtype, attrs, vi, index_img && bary_img && out, N, V, C, F, H, W)) return DRTK_ERR_INVALID_ARGUMENT;
   const size_t es = dtype_size(dtype);
-  DRTK_FOR_VIEW_SLICES(N, n0, n, interpolate_entry(
-      dtype, advance(attrs, n0 * V * C, es), advance_typed(vi, n0 * vi_sN), advance_typed(index_img, n0 * H * W),
-      advance(bary_img, n0 * 3 * H * W, es), n, V, C, F, vi_sN, H, W, advance(out, n0 * C * H * W, es), zero_background, stream))
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == DRTK_F32)
-    return interpolate_impl<float>(static_cast<const float*>(attrs), vi, index_img, static_cast<const float*>(bary_img), N, V, C, vi_sN, H, W, static_cast<float*>(out), zero_background, s);
-  return interpolate_impl<double>(static_cast<const double*>(attrs), vi, index_img, static_cast<const double*>(bary_img), N, V, C, vi_sN, H, W, static_cast<double*>(out), zero_background, s);
+  if (N > kMaxViewsPerLaunch) return for_view_slices(N, [&](int64_t n0, int64_t n) {
+    return interpolate_entry(
+        dtype, advance(attrs, n0 * V * C, es), advance_typed(vi, n0 * vi_sN), advance_typed(index_img, n0 * H * W),
+        advance(bary_img, n0 * 3 * H * W, es), n, V, C, F, vi_sN, H, W, advance(out, n0 * C * H * W, es), zero_background, stream);
+  });
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return interpolate_impl<T>(
+        static_cast<const T*>(attrs), vi, index_img, static_cast<const T*>(bary_img), N, V, C, vi_sN, H, W, static_cast<T*>(out),
+        zero_background, static_cast<hipStream_t>(stream));
+  });
 }
 
 extern "C" int drtk_amd_interpolate(
@@ -1235,11 +1238,13 @@ extern "C" int drtk_amd_interpolate_masked(
 // The workspace is the padded rows of the plan: the size is asked of the plan itself -- both gradients wanted, a workspace that
 // is usable -- and is zero wherever it does not pad (the plan's padding depends on neither the image size nor the alignment).
 extern "C" int drtk_amd_interpolate_backward_workspace_bytes(drtk_dtype_t dtype, int64_t N, int64_t V, int64_t C, size_t* bytes) {
-  if (!bytes || N < 0 || V < 0 || C < 0 || (dtype != DRTK_F32 && dtype != DRTK_F64)) return DRTK_ERR_INVALID_ARGUMENT;
-  const BackwardPlan p = dtype == DRTK_F32 ? plan_backward<float>(C, 0, true, true, true, true, false, false)
-                                           : plan_backward<double>(C, 0, true, true, true, true, false, false);
-  *bytes = (p.padded && N * V > 0) ? dtype_size(dtype) * size_t(N * V * p.CG) : 0;
-  return DRTK_OK;
+  if (!bytes || N < 0 || V < 0 || C < 0) return DRTK_ERR_INVALID_ARGUMENT;
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    const BackwardPlan p = plan_backward<T>(C, 0, true, true, true, true, false, false);
+    *bytes = (p.padded && N * V > 0) ? sizeof(T) * size_t(N * V * p.CG) : 0;
+    return DRTK_OK;
+  });
 }
 
 extern "C" int drtk_amd_interpolate_backward_ws(
@@ -1258,14 +1263,18 @@ extern "C" int drtk_amd_interpolate_backward_ws(
   if (workspace && reinterpret_cast<uintptr_t>(workspace) % 64 != 0) return DRTK_ERR_INVALID_ARGUMENT; // rows of whole 64-byte segments
   const size_t es = dtype_size(dtype);
   // (slices of views reuse the workspace: each call leaves nothing in it)
-  DRTK_FOR_VIEW_SLICES(N, n0, n, drtk_amd_interpolate_backward_ws(
-      dtype, advance(grad_out, n0 * C * H * W, es), advance(attrs, n0 * V * C, es), advance_typed(vi, n0 * vi_sN),
-      advance_typed(index_img, n0 * H * W), advance(bary_img, n0 * 3 * H * W, es), n, V, C, F, vi_sN, H, W,
-      advance(attr_grad, n0 * V * C, es), advance(bary_grad, n0 * 3 * H * W, es), workspace, workspace_bytes, stream))
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == DRTK_F32)
-    return interpolate_backward_impl<float>(static_cast<const float*>(grad_out), static_cast<const float*>(attrs), vi, index_img, static_cast<const float*>(bary_img), N, V, C, vi_sN, H, W, static_cast<float*>(attr_grad), static_cast<float*>(bary_grad), static_cast<float*>(workspace), workspace_bytes, s);
-  return interpolate_backward_impl<double>(static_cast<const double*>(grad_out), static_cast<const double*>(attrs), vi, index_img, static_cast<const double*>(bary_img), N, V, C, vi_sN, H, W, static_cast<double*>(attr_grad), static_cast<double*>(bary_grad), static_cast<double*>(workspace), workspace_bytes, s);
+  if (N > kMaxViewsPerLaunch) return for_view_slices(N, [&](int64_t n0, int64_t n) {
+    return drtk_amd_interpolate_backward_ws(
+        dtype, advance(grad_out, n0 * C * H * W, es), advance(attrs, n0 * V * C, es), advance_typed(vi, n0 * vi_sN),
+        advance_typed(index_img, n0 * H * W), advance(bary_img, n0 * 3 * H * W, es), n, V, C, F, vi_sN, H, W,
+        advance(attr_grad, n0 * V * C, es), advance(bary_grad, n0 * 3 * H * W, es), workspace, workspace_bytes, stream);
+  });
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return interpolate_backward_impl<T>(
+        static_cast<const T*>(grad_out), static_cast<const T*>(attrs), vi, index_img, static_cast<const T*>(bary_img), N, V, C, vi_sN, H, W,
+        static_cast<T*>(attr_grad), static_cast<T*>(bary_grad), static_cast<T*>(workspace), workspace_bytes, static_cast<hipStream_t>(stream));
+  });
 }
 
 extern "C" int drtk_amd_interpolate_backward(

@@ -1958,19 +1958,6 @@ bool planes_fit_32bit(const LevelTable& lv, int mipmaps) {
   return true;
 }
 
-// A run-time padding mode, align_corners or channel count as a compile-time constant: f(Int<V>{}) for the V of LO ... HI that
-// equals v (the entry points have checked the range; anything else takes HI).
-template <int V>
-using Int = std::integral_constant<int, V>;
-template <int LO, int HI, typename F>
-void with_constant(int v, F&& f) {
-  if constexpr (LO == HI) {
-    f(Int<LO>{});
-  } else {
-    if (v == LO) f(Int<LO>{}); else with_constant<LO + 1, HI>(v, f);
-  }
-}
-
 // The argument check of both entry points, complete before either writes anything (tests/test_mipmap_args_host.py pins every
 // status; tests/test_gpu_mipmap_rejects.py that a rejected backward call has written nothing).  `grad_levels`: null in the
 // forward.  `result`: the forward's `out`, the backward's `grad_grid`.  The per-pixel pointers and the grid layouts are judged
@@ -1981,14 +1968,15 @@ int check_sampler_args(
     const int64_t* level_sN, int mipmaps, const void* grid, const int64_t* grid_layout, const void* vt_dxdy_img, int64_t N, int64_t C,
     int64_t H, int64_t W, int max_aniso, int padding_mode, int interpolation_mode, const void* grad_out, const void* result,
     const int64_t* grad_grid_layout, LevelTable& lv, GridLayout& gl, GridLayout& ggl) {
+  // (not bad_image(): this check puts no bound on H W)
   if (N < 0 || C < 0 || H < 0 || W < 0 || C >= (1 << 20) || max_aniso < 1 || padding_mode < 0 || padding_mode > 2 ||
-      (interpolation_mode != 0 && interpolation_mode != 2) || (dtype != DRTK_F32 && dtype != DRTK_F64) || (backward && !grad_levels))
+      (interpolation_mode != 0 && interpolation_mode != 2) || !valid_dtype(dtype) || (backward && !grad_levels))
     return DRTK_ERR_INVALID_ARGUMENT;
   const int st = fill_table(lv, levels, grad_levels, level_h, level_w, level_sN, mipmaps, N, C);
   if (st != DRTK_OK) return st;
   if (N * H * W == 0 || (!backward && C == 0)) return DRTK_OK;
   if (!grid || !vt_dxdy_img || !result || (backward && C > 0 && !grad_out)) return DRTK_ERR_INVALID_ARGUMENT;
-  const size_t es = dtype == DRTK_F32 ? 4 : 8;
+  const size_t es = dtype_size(dtype);
   if (make_grid_layout(gl, grid_layout, grid, H, W, es) != DRTK_OK) return DRTK_ERR_INVALID_ARGUMENT;
   if (backward && make_grid_layout(ggl, grad_grid_layout, result, H, W, es) != DRTK_OK) return DRTK_ERR_INVALID_ARGUMENT;
   return DRTK_OK;
@@ -2030,7 +2018,7 @@ extern "C" int drtk_amd_mipmap_grid_sampler_2d(
   if (count == 0 || C == 0) return DRTK_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const SamplerRoute route = sampler_route(interpolation_mode, N, C, lv, mipmaps, false);
-  auto launch = [&](auto tag) {
+  return dispatch_dtype(dtype, [&](auto tag) {
     using T = decltype(tag);
     const T* grid_t = static_cast<const T*>(grid);
     const T* vt = static_cast<const T*>(vt_dxdy_img);
@@ -2056,10 +2044,9 @@ extern "C" int drtk_amd_mipmap_grid_sampler_2d(
         });
       }
     });
-  };
-  if (dtype == DRTK_F32) launch(float{}); else launch(double{});
-  DRTK_RETURN_IF_LAUNCH_FAILED();
-  return DRTK_OK;
+    DRTK_RETURN_IF_LAUNCH_FAILED();
+    return DRTK_OK;
+  });
 }
 
 extern "C" int drtk_amd_mipmap_grid_sampler_2d_backward(
@@ -2075,7 +2062,7 @@ extern "C" int drtk_amd_mipmap_grid_sampler_2d_backward(
       interpolation_mode, grad_out, grad_grid, grad_grid_layout, lv, gl, ggl);
   if (st != DRTK_OK) return st;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const size_t es = dtype == DRTK_F32 ? 4 : 8;
+  const size_t es = dtype_size(dtype);
   // :1120-1123 zeros_like -- also for a call with textures and no pixels.  Levels that lie back to back in memory (a caller that
   // carves the gradient pyramid out of one buffer, like the torch shim) are zeroed by one launch: the coarse levels are a few KB
   // each and a launch costs more than their fill.
@@ -2093,7 +2080,7 @@ extern "C" int drtk_amd_mipmap_grid_sampler_2d_backward(
   const int64_t count = N * H * W;
   if (count == 0) return DRTK_OK;
   const SamplerRoute route = sampler_route(interpolation_mode, N, C, lv, mipmaps, DRTK_DBG(debug_flags(), 512));
-  auto launch = [&](auto tag) -> int {
+  return dispatch_dtype(dtype, [&](auto tag) -> int {
     using T = decltype(tag);
     const T* gout = static_cast<const T*>(grad_out);
     const T* grid_t = static_cast<const T*>(grid);
@@ -2143,6 +2130,5 @@ extern "C" int drtk_amd_mipmap_grid_sampler_2d_backward(
       });
     });
     return rc;
-  };
-  return dtype == DRTK_F32 ? launch(float{}) : launch(double{});
+  });
 }

@@ -301,9 +301,9 @@ int pyramid_max_levels(int64_t H, int64_t W) {
 // what is judged before any pointer: dtype, sizes, levels
 int pyramid_validate(drtk_dtype_t dtype, int64_t N, int64_t C, int64_t H, int64_t W, int levels) {
   constexpr int64_t kLimit = int64_t(1) << 31;
-  if (dtype != DRTK_F32 && dtype != DRTK_F64) return DRTK_ERR_INVALID_ARGUMENT;
-  if (N < 0 || C < 0 || H < 0 || W < 0 || C >= kLimit || H >= kLimit || W >= kLimit) return DRTK_ERR_INVALID_ARGUMENT;
-  if (H * W >= kLimit) return DRTK_ERR_INVALID_ARGUMENT;
+  if (!valid_dtype(dtype)) return DRTK_ERR_INVALID_ARGUMENT;
+  // (H and W also one by one: an empty image of 2^31 rows is invalid here)
+  if (C < 0 || C >= kLimit || H >= kLimit || W >= kLimit || bad_image(N, H, W)) return DRTK_ERR_INVALID_ARGUMENT;
   if (levels < 1 || levels > kPyramidMaxLevels) return DRTK_ERR_INVALID_ARGUMENT;
   if (H * W > 0 && levels > pyramid_max_levels(H, W)) return DRTK_ERR_INVALID_ARGUMENT;
   if (N > 0 && H * W > 0 && C < 1) return DRTK_ERR_INVALID_ARGUMENT;
@@ -384,32 +384,23 @@ extern "C" int drtk_amd_mipmap_pyramid(
     if (!out[l] || out_sN[l] < 0) return DRTK_ERR_INVALID_ARGUMENT;
   }
   const size_t es = dtype_size(dtype);
-  if (N > kMaxViewsPerLaunch) {
-    for (int64_t n0 = 0; n0 < N; n0 += kMaxViewsPerLaunch) {
-      const int64_t n = N - n0 < kMaxViewsPerLaunch ? N - n0 : kMaxViewsPerLaunch;
-      void* slice[kPyramidMaxLevels] = {};
-      for (int l = 1; l < levels; ++l) slice[l] = advance(out[l], n0 * out_sN[l], es);
-      const int rc =
-          drtk_amd_mipmap_pyramid(dtype, advance(input, n0 * input_sN, es), input_sN, input_sC, n, C, H, W, levels, slice, out_sN, stream);
-      if (rc != DRTK_OK) return rc;
-    }
-    return DRTK_OK;
-  }
+  if (N > kMaxViewsPerLaunch) return for_view_slices(N, [&](int64_t n0, int64_t n) {
+    void* slice[kPyramidMaxLevels] = {};
+    for (int l = 1; l < levels; ++l) slice[l] = advance(out[l], n0 * out_sN[l], es);
+    return drtk_amd_mipmap_pyramid(dtype, advance(input, n0 * input_sN, es), input_sN, input_sC, n, C, H, W, levels, slice, out_sN, stream);
+  });
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int first = levels - 1 < kTileLevels ? levels - 1 : kTileLevels; // levels 1 .. first from the input
   const int second = levels - 1 - first;                                 // levels 7 .. from level 6 as stored
   const int64_t h6 = H >> kTileLevels, w6 = W >> kTileLevels;
-  if (dtype == DRTK_F32) {
-    pyramid_forward_launch<float>(input, input_sN, input_sC, N, C, H, W, out + 1, out_sN + 1, first, s);
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    pyramid_forward_launch<T>(input, input_sN, input_sC, N, C, H, W, out + 1, out_sN + 1, first, s);
     if (second > 0)
-      pyramid_forward_launch<float>(out[kTileLevels], out_sN[kTileLevels], h6 * w6, N, C, h6, w6, out + 1 + kTileLevels, out_sN + 1 + kTileLevels, second, s);
-  } else {
-    pyramid_forward_launch<double>(input, input_sN, input_sC, N, C, H, W, out + 1, out_sN + 1, first, s);
-    if (second > 0)
-      pyramid_forward_launch<double>(out[kTileLevels], out_sN[kTileLevels], h6 * w6, N, C, h6, w6, out + 1 + kTileLevels, out_sN + 1 + kTileLevels, second, s);
-  }
-  DRTK_RETURN_IF_LAUNCH_FAILED();
-  return DRTK_OK;
+      pyramid_forward_launch<T>(out[kTileLevels], out_sN[kTileLevels], h6 * w6, N, C, h6, w6, out + 1 + kTileLevels, out_sN + 1 + kTileLevels, second, s);
+    DRTK_RETURN_IF_LAUNCH_FAILED();
+    return DRTK_OK;
+  });
 }
 
 extern "C" int drtk_amd_mipmap_pyramid_backward(
@@ -423,22 +414,15 @@ extern "C" int drtk_amd_mipmap_pyramid_backward(
     if (grad_levels[l] && grad_sN[l] < 0) return DRTK_ERR_INVALID_ARGUMENT;
   }
   const size_t es = dtype_size(dtype);
-  if (N > kMaxViewsPerLaunch) {
-    for (int64_t n0 = 0; n0 < N; n0 += kMaxViewsPerLaunch) {
-      const int64_t n = N - n0 < kMaxViewsPerLaunch ? N - n0 : kMaxViewsPerLaunch;
-      const void* slice[kPyramidMaxLevels] = {};
-      for (int l = 0; l < levels; ++l) slice[l] = advance(grad_levels[l], n0 * grad_sN[l], es);
-      const int rc = drtk_amd_mipmap_pyramid_backward(dtype, slice, grad_sN, n, C, H, W, levels, advance(grad_input, n0 * C * H * W, es), stream);
-      if (rc != DRTK_OK) return rc;
-    }
+  if (N > kMaxViewsPerLaunch) return for_view_slices(N, [&](int64_t n0, int64_t n) {
+    const void* slice[kPyramidMaxLevels] = {};
+    for (int l = 0; l < levels; ++l) slice[l] = advance(grad_levels[l], n0 * grad_sN[l], es);
+    return drtk_amd_mipmap_pyramid_backward(dtype, slice, grad_sN, n, C, H, W, levels, advance(grad_input, n0 * C * H * W, es), stream);
+  });
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    pyramid_backward_launch<T>(grad_levels, grad_sN, N, C, H, W, levels, grad_input, static_cast<hipStream_t>(stream));
+    DRTK_RETURN_IF_LAUNCH_FAILED();
     return DRTK_OK;
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == DRTK_F32) {
-    pyramid_backward_launch<float>(grad_levels, grad_sN, N, C, H, W, levels, grad_input, s);
-  } else {
-    pyramid_backward_launch<double>(grad_levels, grad_sN, N, C, H, W, levels, grad_input, s);
-  }
-  DRTK_RETURN_IF_LAUNCH_FAILED();
-  return DRTK_OK;
+  });
 }

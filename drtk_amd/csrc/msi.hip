@@ -216,9 +216,10 @@ int msi_validate(
     drtk_dtype_t dtype, int64_t N, int64_t L, int64_t H, int64_t W, int sub_step_count, double min_inv_r, double max_inv_r,
     double stop_thresh) {
   constexpr int64_t kLimit = int64_t(1) << 31;
-  if (dtype != DRTK_F32 && dtype != DRTK_F64) return DRTK_ERR_INVALID_ARGUMENT;
-  if (N < 0 || N >= kLimit || L < 0 || H < 0 || W < 0 || L >= kLimit || H >= kLimit || W >= kLimit) return DRTK_ERR_INVALID_ARGUMENT;
-  if (H * W >= kLimit || L * 4 * (H * W) >= kLimit) return DRTK_ERR_INVALID_ARGUMENT;
+  if (!valid_dtype(dtype)) return DRTK_ERR_INVALID_ARGUMENT;
+  // (N counts rays, not views, and the whole texture is indexed in 31 bits, not one image: bounds of this file's own)
+  if (N >= kLimit || L < 0 || L >= kLimit || H >= kLimit || W >= kLimit || bad_image(N, H, W)) return DRTK_ERR_INVALID_ARGUMENT;
+  if (L * 4 * (H * W) >= kLimit) return DRTK_ERR_INVALID_ARGUMENT;
   if (sub_step_count < 1 || L * sub_step_count >= kLimit) return DRTK_ERR_INVALID_ARGUMENT;
   if (!(min_inv_r > max_inv_r) || !(stop_thresh > 0.0 && stop_thresh < 1.0)) return DRTK_ERR_INVALID_ARGUMENT; // (NaN fails too)
   return DRTK_OK;
@@ -228,15 +229,6 @@ int msi_validate(
 } // namespace drtk_amd
 
 using namespace drtk_amd;
-
-#define MSI_DISPATCH(LAUNCH)      \
-  do {                            \
-    if (dtype == DRTK_F32) {      \
-      LAUNCH(float);              \
-    } else {                      \
-      LAUNCH(double);             \
-    }                             \
-  } while (0)
 
 extern "C" int drtk_amd_msi_forward(
     drtk_dtype_t dtype, const float* ray_o, const float* ray_d, const void* texture, int64_t N, int64_t L, int64_t H, int64_t W,
@@ -248,14 +240,14 @@ extern "C" int drtk_amd_msi_forward(
   hipStream_t s = static_cast<hipStream_t>(stream);
   const dim3 grid_dim(static_cast<unsigned>(ceil_div(N, kBlock)));
   const int n = static_cast<int>(L * sub_step_count);
-#define MSI_FWD(T)                                                                                                       \
-  DRTK_LAUNCH(                                                                                                           \
-      (msi_forward_kernel<T>), grid_dim, dim3(kBlock), 0, s, ray_o, ray_d, static_cast<const T*>(texture), N, (int)L,    \
-      (int)H, (int)W, n, min_inv_r, max_inv_r, stop_thresh, static_cast<T*>(out))
-  MSI_DISPATCH(MSI_FWD);
-#undef MSI_FWD
-  DRTK_RETURN_IF_LAUNCH_FAILED();
-  return DRTK_OK;
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    DRTK_LAUNCH(
+        (msi_forward_kernel<T>), grid_dim, dim3(kBlock), 0, s, ray_o, ray_d, static_cast<const T*>(texture), N, (int)L, (int)H, (int)W, n,
+        min_inv_r, max_inv_r, stop_thresh, static_cast<T*>(out));
+    DRTK_RETURN_IF_LAUNCH_FAILED();
+    return DRTK_OK;
+  });
 }
 
 extern "C" int drtk_amd_msi_backward(
@@ -272,13 +264,12 @@ extern "C" int drtk_amd_msi_backward(
   if (N == 0) return DRTK_OK;
   const dim3 grid_dim(static_cast<unsigned>(ceil_div(N, kBlock)));
   const int n = static_cast<int>(L * sub_step_count);
-#define MSI_BWD(T)                                                                                                        \
-  DRTK_LAUNCH(                                                                                                            \
-      (msi_backward_kernel<T>), grid_dim, dim3(kBlock), 0, s, static_cast<const T*>(grad_out), static_cast<const T*>(out), \
-      ray_o, ray_d, static_cast<const T*>(texture), N, (int)L, (int)H, (int)W, n, min_inv_r, max_inv_r, stop_thresh,      \
-      static_cast<T*>(grad_texture))
-  MSI_DISPATCH(MSI_BWD);
-#undef MSI_BWD
-  DRTK_RETURN_IF_LAUNCH_FAILED();
-  return DRTK_OK;
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    DRTK_LAUNCH(
+        (msi_backward_kernel<T>), grid_dim, dim3(kBlock), 0, s, static_cast<const T*>(grad_out), static_cast<const T*>(out), ray_o, ray_d,
+        static_cast<const T*>(texture), N, (int)L, (int)H, (int)W, n, min_inv_r, max_inv_r, stop_thresh, static_cast<T*>(grad_texture));
+    DRTK_RETURN_IF_LAUNCH_FAILED();
+    return DRTK_OK;
+  });
 }

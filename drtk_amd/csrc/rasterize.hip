@@ -1623,9 +1623,10 @@ int rasterize_impl(
 int rasterize_dispatch(
     drtk_dtype_t dtype, const void* v, const int32_t* vi, int64_t N, int64_t V, int64_t F, int64_t vi_sN, int64_t H, int64_t W,
     float* depth_img, int32_t* index_img, void* workspace, size_t workspace_bytes, hipStream_t s, int num_layers) {
-  if (dtype == DRTK_F32)
-    return rasterize_impl<float>(static_cast<const float*>(v), vi, N, V, F, vi_sN, H, W, depth_img, index_img, workspace, workspace_bytes, s, num_layers);
-  return rasterize_impl<double>(static_cast<const double*>(v), vi, N, V, F, vi_sN, H, W, depth_img, index_img, workspace, workspace_bytes, s, num_layers);
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return rasterize_impl<T>(static_cast<const T*>(v), vi, N, V, F, vi_sN, H, W, depth_img, index_img, workspace, workspace_bytes, s, num_layers);
+  });
 }
 
 // The argument check of drtk_amd_rasterize and drtk_amd_rasterize_layers, complete before either touches the device
@@ -1635,12 +1636,12 @@ int rasterize_dispatch(
 int check_raster_args(
     drtk_dtype_t dtype, const void* v, const int32_t* vi, int64_t N, int64_t V, int64_t F, int64_t vi_sN, int64_t H, int64_t W,
     int64_t planes, bool wireframe, const float* depth_img, const int32_t* index_img, const void* workspace) {
+  // (not bad_image(): an empty image is invalid here, and the size limits are the tiles' and the bins', below)
   if (N < 0 || V < 0 || F < 0 || H <= 0 || W <= 0) return DRTK_ERR_INVALID_ARGUMENT; // :464-468
   // 64-bit counters / packed pixels updated with 64-bit atomics live in the workspace (include/drtk_amd.h, alignment)
   if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return DRTK_ERR_INVALID_ARGUMENT;
   if (V >= 0x10000000LL) return DRTK_ERR_TOO_MANY_VERTICES; // :459-462
-  if (dtype != DRTK_F32 && dtype != DRTK_F64) return DRTK_ERR_INVALID_ARGUMENT;
-  if (vi_sN != 0 && vi_sN != F * 3) return DRTK_ERR_INVALID_ARGUMENT;
+  if (!valid_dtype(dtype) || bad_view_stride(vi_sN, F * 3)) return DRTK_ERR_INVALID_ARGUMENT;
   // more views than one launch takes: the entry point calls itself on slices, and the limits and pointers are judged there
   if (N > kMaxViewsPerLaunch) return DRTK_OK;
   if (N * planes * H * W >= (int64_t(1) << 40)) return DRTK_ERR_INVALID_ARGUMENT;
@@ -1673,9 +1674,11 @@ extern "C" int drtk_amd_rasterize(
   const int st = check_raster_args(dtype, v, vi, N, V, F, vi_sN, H, W, 1, wireframe != 0, depth_img, index_img, workspace);
   if (st != DRTK_OK) return st;
   // slices, each reusing the workspace (sized for all N: enough for any slice)
-  DRTK_FOR_VIEW_SLICES(N, n0, n, drtk_amd_rasterize(
-      dtype, advance(v, n0 * V * 3, dtype_size(dtype)), advance_typed(vi, n0 * vi_sN), n, V, F, vi_sN, H, W, wireframe,
-      advance_typed(depth_img, n0 * H * W), advance_typed(index_img, n0 * H * W), workspace, workspace_bytes, stream))
+  if (N > kMaxViewsPerLaunch) return for_view_slices(N, [&](int64_t n0, int64_t n) {
+    return drtk_amd_rasterize(
+        dtype, advance(v, n0 * V * 3, dtype_size(dtype)), advance_typed(vi, n0 * vi_sN), n, V, F, vi_sN, H, W, wireframe,
+        advance_typed(depth_img, n0 * H * W), advance_typed(index_img, n0 * H * W), workspace, workspace_bytes, stream);
+  });
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (wireframe) return rasterize_lines_dispatch(dtype, v, vi, N, V, F, vi_sN, H, W, depth_img, index_img, workspace, workspace_bytes, s);
   return rasterize_dispatch(dtype, v, vi, N, V, F, vi_sN, H, W, depth_img, index_img, workspace, workspace_bytes, s, 0);
@@ -1696,9 +1699,11 @@ extern "C" int drtk_amd_rasterize_layers(
   const int64_t K = num_layers;
   const int st = check_raster_args(dtype, v, vi, N, V, F, vi_sN, H, W, K, false, depth_img, index_img, workspace);
   if (st != DRTK_OK) return st;
-  DRTK_FOR_VIEW_SLICES(N, n0, n, drtk_amd_rasterize_layers(
-      dtype, advance(v, n0 * V * 3, dtype_size(dtype)), advance_typed(vi, n0 * vi_sN), n, V, F, vi_sN, H, W, num_layers,
-      advance_typed(depth_img, n0 * K * H * W), advance_typed(index_img, n0 * K * H * W), workspace, workspace_bytes, stream))
+  if (N > kMaxViewsPerLaunch) return for_view_slices(N, [&](int64_t n0, int64_t n) {
+    return drtk_amd_rasterize_layers(
+        dtype, advance(v, n0 * V * 3, dtype_size(dtype)), advance_typed(vi, n0 * vi_sN), n, V, F, vi_sN, H, W, num_layers,
+        advance_typed(depth_img, n0 * K * H * W), advance_typed(index_img, n0 * K * H * W), workspace, workspace_bytes, stream);
+  });
   return rasterize_dispatch(dtype, v, vi, N, V, F, vi_sN, H, W, depth_img, index_img, workspace, workspace_bytes, static_cast<hipStream_t>(stream), num_layers);
 }
 
@@ -1708,13 +1713,10 @@ extern "C" int drtk_amd_selftest_exact_div(
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (fill_bytes_async(d_mismatches, 0, sizeof(uint64_t), s) != DRTK_OK) return DRTK_ERR_LAUNCH;
   const unsigned blocks = 4096;
-  if (dtype == DRTK_F32) {
-    DRTK_LAUNCH((exact_div_selftest_kernel<float>), dim3(blocks), dim3(kBlock), 0, s, seed, (long long)count, (unsigned long long*)d_mismatches);
-  } else if (dtype == DRTK_F64) {
-    DRTK_LAUNCH((exact_div_selftest_kernel<double>), dim3(blocks), dim3(kBlock), 0, s, seed, (long long)count, (unsigned long long*)d_mismatches);
-  } else {
-    return DRTK_ERR_INVALID_ARGUMENT;
-  }
-  DRTK_RETURN_IF_LAUNCH_FAILED();
-  return DRTK_OK;
+  return dispatch_dtype(dtype, [&](auto tag) { // (as before: a bad dtype is found behind the clear)
+    using T = decltype(tag);
+    DRTK_LAUNCH((exact_div_selftest_kernel<T>), dim3(blocks), dim3(kBlock), 0, s, seed, (long long)count, (unsigned long long*)d_mismatches);
+    DRTK_RETURN_IF_LAUNCH_FAILED();
+    return DRTK_OK;
+  });
 }

@@ -173,12 +173,13 @@ int rasterize_lines_dispatch(
   if (fill_bytes_async(packed, 0xFF, sizeof(unsigned long long) * count, stream) != DRTK_OK) return DRTK_ERR_LAUNCH; // :484-488
   if (N * F > 0) {
     const dim3 grid(static_cast<unsigned>(ceil_div(F, kBlock / kWave)), static_cast<unsigned>(N));
-    if (dtype == DRTK_F32) {
-      DRTK_LAUNCH((rasterize_lines_kernel<float>), grid, dim3(kBlock), 0, stream, static_cast<const float*>(v), vi, (int)F, V, vi_sN, (int)H, (int)W, packed);
-    } else {
-      DRTK_LAUNCH((rasterize_lines_kernel<double>), grid, dim3(kBlock), 0, stream, static_cast<const double*>(v), vi, (int)F, V, vi_sN, (int)H, (int)W, packed);
-    }
-    DRTK_RETURN_IF_LAUNCH_FAILED();
+    const int st = dispatch_dtype(dtype, [&](auto tag) {
+      using T = decltype(tag);
+      DRTK_LAUNCH((rasterize_lines_kernel<T>), grid, dim3(kBlock), 0, stream, static_cast<const T*>(v), vi, (int)F, V, vi_sN, (int)H, (int)W, packed);
+      DRTK_RETURN_IF_LAUNCH_FAILED();
+      return DRTK_OK;
+    });
+    if (st != DRTK_OK) return st;
   }
   DRTK_LAUNCH(unpack_lines_kernel, dim3(static_cast<unsigned>(ceil_div(count, kBlock))), dim3(kBlock), 0, stream, packed, count, depth_img, index_img);
   DRTK_RETURN_IF_LAUNCH_FAILED();

@@ -402,9 +402,16 @@ int render_backward_impl(
   return DRTK_OK;
 }
 
-bool bad_common(int64_t N, int64_t V, int64_t F, int64_t vi_sN, int64_t H, int64_t W) {
-  return N < 0 || V < 0 || F < 0 || H < 0 || W < 0 || (vi_sN != 0 && vi_sN != F * 3) ||
-      H * W >= (int64_t(1) << 31);
+// The argument check of both entry points, complete before either writes anything (tests/test_render_args_host.py pins every
+// status).  `depth`, `bary`: the forward's outputs, the backward's incoming gradients.  `grad_v`: the backward's output (null in
+// the forward), cleared -- so required -- as soon as there is a vertex, pixels or not.
+int check_render_args(
+    bool backward, drtk_dtype_t dtype, const void* v, const int32_t* vi, const int32_t* index_img, const void* depth, const void* bary,
+    int64_t N, int64_t V, int64_t F, int64_t vi_sN, int64_t H, int64_t W, const void* grad_v) {
+  if (bad_image(N, H, W) || V < 0 || F < 0 || bad_view_stride(vi_sN, F * 3) || !valid_dtype(dtype)) return DRTK_ERR_INVALID_ARGUMENT;
+  if (N * H * W > 0 && (!index_img || !depth || !bary)) return DRTK_ERR_INVALID_ARGUMENT;
+  if ((N * V > 0 && (!v || (backward && !grad_v))) || (F > 0 && !vi)) return DRTK_ERR_INVALID_ARGUMENT;
+  return DRTK_OK;
 }
 
 } // namespace
@@ -416,46 +423,39 @@ extern "C" int drtk_amd_render(
     drtk_dtype_t dtype, const void* v, const int32_t* vi, const int32_t* index_img, int64_t N,
     int64_t V, int64_t F, int64_t vi_sN, int64_t H, int64_t W, void* depth_img, void* bary_img,
     drtk_stream_t stream) {
-  if (bad_common(N, V, F, vi_sN, H, W)) return DRTK_ERR_INVALID_ARGUMENT;
-  if (N * H * W > 0 && (!index_img || !depth_img || !bary_img)) return DRTK_ERR_INVALID_ARGUMENT;
-  if ((N * V > 0 && !v) || (F > 0 && !vi)) return DRTK_ERR_INVALID_ARGUMENT;
-  if (dtype != DRTK_F32 && dtype != DRTK_F64) return DRTK_ERR_INVALID_ARGUMENT;
+  const int st = check_render_args(false, dtype, v, vi, index_img, depth_img, bary_img, N, V, F, vi_sN, H, W, nullptr);
+  if (st != DRTK_OK) return st;
   const size_t es = dtype_size(dtype);
-  DRTK_FOR_VIEW_SLICES(N, n0, n, drtk_amd_render(
-      dtype, advance(v, n0 * V * 3, es), advance_typed(vi, n0 * vi_sN), advance_typed(index_img, n0 * H * W), n, V, F, vi_sN, H, W,
-      advance(depth_img, n0 * H * W, es), advance(bary_img, n0 * 3 * H * W, es), stream))
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (dtype) {
-    case DRTK_F32:
-      return render_impl<float>(static_cast<const float*>(v), vi, index_img, N, V, vi_sN, H, W, static_cast<float*>(depth_img), static_cast<float*>(bary_img), s);
-    case DRTK_F64:
-      return render_impl<double>(static_cast<const double*>(v), vi, index_img, N, V, vi_sN, H, W, static_cast<double*>(depth_img), static_cast<double*>(bary_img), s);
-    default:
-      return DRTK_ERR_INVALID_ARGUMENT;
-  }
+  if (N > kMaxViewsPerLaunch) return for_view_slices(N, [&](int64_t n0, int64_t n) {
+    return drtk_amd_render(
+        dtype, advance(v, n0 * V * 3, es), advance_typed(vi, n0 * vi_sN), advance_typed(index_img, n0 * H * W), n, V, F, vi_sN, H, W,
+        advance(depth_img, n0 * H * W, es), advance(bary_img, n0 * 3 * H * W, es), stream);
+  });
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return render_impl<T>(
+        static_cast<const T*>(v), vi, index_img, N, V, vi_sN, H, W, static_cast<T*>(depth_img), static_cast<T*>(bary_img),
+        static_cast<hipStream_t>(stream));
+  });
 }
 
 extern "C" int drtk_amd_render_backward(
     drtk_dtype_t dtype, const void* v, const int32_t* vi, const int32_t* index_img,
     const void* grad_depth_img, const void* grad_bary_img, int64_t N, int64_t V, int64_t F,
     int64_t vi_sN, int64_t H, int64_t W, void* grad_v, drtk_stream_t stream) {
-  if (bad_common(N, V, F, vi_sN, H, W)) return DRTK_ERR_INVALID_ARGUMENT;
-  if (N * V > 0 && !grad_v) return DRTK_ERR_INVALID_ARGUMENT;
-  if (N * H * W > 0 && (!index_img || !grad_depth_img || !grad_bary_img)) return DRTK_ERR_INVALID_ARGUMENT;
-  if ((N * V > 0 && !v) || (F > 0 && !vi)) return DRTK_ERR_INVALID_ARGUMENT;
-  if (dtype != DRTK_F32 && dtype != DRTK_F64) return DRTK_ERR_INVALID_ARGUMENT;
+  const int st = check_render_args(true, dtype, v, vi, index_img, grad_depth_img, grad_bary_img, N, V, F, vi_sN, H, W, grad_v);
+  if (st != DRTK_OK) return st;
   const size_t es = dtype_size(dtype);
-  DRTK_FOR_VIEW_SLICES(N, n0, n, drtk_amd_render_backward(
-      dtype, advance(v, n0 * V * 3, es), advance_typed(vi, n0 * vi_sN), advance_typed(index_img, n0 * H * W),
-      advance(grad_depth_img, n0 * H * W, es), advance(grad_bary_img, n0 * 3 * H * W, es), n, V, F, vi_sN, H, W,
-      advance(grad_v, n0 * V * 3, es), stream))
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (dtype) {
-    case DRTK_F32:
-      return render_backward_impl<float>(static_cast<const float*>(v), vi, index_img, static_cast<const float*>(grad_depth_img), static_cast<const float*>(grad_bary_img), N, V, vi_sN, H, W, static_cast<float*>(grad_v), s);
-    case DRTK_F64:
-      return render_backward_impl<double>(static_cast<const double*>(v), vi, index_img, static_cast<const double*>(grad_depth_img), static_cast<const double*>(grad_bary_img), N, V, vi_sN, H, W, static_cast<double*>(grad_v), s);
-    default:
-      return DRTK_ERR_INVALID_ARGUMENT;
-  }
+  if (N > kMaxViewsPerLaunch) return for_view_slices(N, [&](int64_t n0, int64_t n) {
+    return drtk_amd_render_backward(
+        dtype, advance(v, n0 * V * 3, es), advance_typed(vi, n0 * vi_sN), advance_typed(index_img, n0 * H * W),
+        advance(grad_depth_img, n0 * H * W, es), advance(grad_bary_img, n0 * 3 * H * W, es), n, V, F, vi_sN, H, W,
+        advance(grad_v, n0 * V * 3, es), stream);
+  });
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return render_backward_impl<T>(
+        static_cast<const T*>(v), vi, index_img, static_cast<const T*>(grad_depth_img), static_cast<const T*>(grad_bary_img), N, V,
+        vi_sN, H, W, static_cast<T*>(grad_v), static_cast<hipStream_t>(stream));
+  });
 }

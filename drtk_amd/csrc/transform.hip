@@ -129,6 +129,16 @@ int transform_backward_impl(const T* v, int64_t v_sN, const T* campos, const T* 
   return DRTK_OK;
 }
 
+// The argument check of both entry points (tests/test_transform_args_host.py pins every status).  `in`: the backward's
+// grad_v_pix (null in the forward); `out`: v_pix or grad_v.  The forward's v_cam is optional.  No image here: the limit is on V.
+int check_transform_args(
+    bool backward, drtk_dtype_t dtype, const void* v, int64_t v_sN, const void* campos, const void* camrot, const void* focal,
+    const void* princpt, const void* in, int64_t N, int64_t V, const void* out) {
+  if (N < 0 || V < 0 || V >= (int64_t(1) << 31) || bad_view_stride(v_sN, V * 3) || !valid_dtype(dtype)) return DRTK_ERR_INVALID_ARGUMENT;
+  if (N * V > 0 && (!v || !campos || !camrot || !focal || !princpt || (backward && !in) || !out)) return DRTK_ERR_INVALID_ARGUMENT;
+  return DRTK_OK;
+}
+
 } // namespace
 } // namespace drtk_amd
 
@@ -138,44 +148,39 @@ extern "C" int drtk_amd_transform_pinhole(
     drtk_dtype_t dtype, const void* v, int64_t v_sN, const void* campos, const void* camrot,
     const void* focal, const void* princpt, int64_t N, int64_t V, void* v_pix, void* v_cam,
     drtk_stream_t stream) {
-  if (N < 0 || V < 0 || V >= (int64_t(1) << 31) || (v_sN != 0 && v_sN != V * 3)) return DRTK_ERR_INVALID_ARGUMENT;
-  if (N * V > 0 && (!v || !campos || !camrot || !focal || !princpt || !v_pix)) return DRTK_ERR_INVALID_ARGUMENT;
-  if (dtype != DRTK_F32 && dtype != DRTK_F64) return DRTK_ERR_INVALID_ARGUMENT;
+  const int st = check_transform_args(false, dtype, v, v_sN, campos, camrot, focal, princpt, nullptr, N, V, v_pix);
+  if (st != DRTK_OK) return st;
   const size_t es = dtype_size(dtype);
-  DRTK_FOR_VIEW_SLICES(N, n0, n, drtk_amd_transform_pinhole(
-      dtype, advance(v, n0 * v_sN, es), v_sN, advance(campos, n0 * 3, es), advance(camrot, n0 * 9, es), advance(focal, n0 * 4, es),
-      advance(princpt, n0 * 2, es), n, V, advance(v_pix, n0 * V * 3, es), advance(v_cam, n0 * V * 3, es), stream))
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (dtype) {
-    case DRTK_F32:
-      return transform_impl<float>(static_cast<const float*>(v), v_sN, static_cast<const float*>(campos), static_cast<const float*>(camrot), static_cast<const float*>(focal), static_cast<const float*>(princpt), N, V, static_cast<float*>(v_pix), static_cast<float*>(v_cam), s);
-    case DRTK_F64:
-      return transform_impl<double>(static_cast<const double*>(v), v_sN, static_cast<const double*>(campos), static_cast<const double*>(camrot), static_cast<const double*>(focal), static_cast<const double*>(princpt), N, V, static_cast<double*>(v_pix), static_cast<double*>(v_cam), s);
-    default:
-      return DRTK_ERR_INVALID_ARGUMENT;
-  }
+  if (N > kMaxViewsPerLaunch) return for_view_slices(N, [&](int64_t n0, int64_t n) {
+    return drtk_amd_transform_pinhole(
+        dtype, advance(v, n0 * v_sN, es), v_sN, advance(campos, n0 * 3, es), advance(camrot, n0 * 9, es), advance(focal, n0 * 4, es),
+        advance(princpt, n0 * 2, es), n, V, advance(v_pix, n0 * V * 3, es), advance(v_cam, n0 * V * 3, es), stream);
+  });
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return transform_impl<T>(
+        static_cast<const T*>(v), v_sN, static_cast<const T*>(campos), static_cast<const T*>(camrot), static_cast<const T*>(focal),
+        static_cast<const T*>(princpt), N, V, static_cast<T*>(v_pix), static_cast<T*>(v_cam), static_cast<hipStream_t>(stream));
+  });
 }
 
 extern "C" int drtk_amd_transform_pinhole_backward(
     drtk_dtype_t dtype, const void* v, int64_t v_sN, const void* campos, const void* camrot,
     const void* focal, const void* princpt, const void* grad_v_pix, int64_t N, int64_t V,
     void* grad_v, drtk_stream_t stream) {
-  if (N < 0 || V < 0 || V >= (int64_t(1) << 31) || (v_sN != 0 && v_sN != V * 3)) return DRTK_ERR_INVALID_ARGUMENT;
-  if (N * V > 0 && (!v || !campos || !camrot || !focal || !princpt || !grad_v_pix || !grad_v)) return DRTK_ERR_INVALID_ARGUMENT;
-  if (dtype != DRTK_F32 && dtype != DRTK_F64) return DRTK_ERR_INVALID_ARGUMENT;
-  if (v_sN != 0) { // per-view vertices: views are independent (shared vertices: ONE launch sums the views in-kernel, any N)
-    const size_t es = dtype_size(dtype);
-    DRTK_FOR_VIEW_SLICES(N, n0, n, drtk_amd_transform_pinhole_backward(
+  const int st = check_transform_args(true, dtype, v, v_sN, campos, camrot, focal, princpt, grad_v_pix, N, V, grad_v);
+  if (st != DRTK_OK) return st;
+  const size_t es = dtype_size(dtype);
+  // per-view vertices: views are independent (shared vertices: ONE launch sums the views in-kernel, any N)
+  if (v_sN != 0 && N > kMaxViewsPerLaunch) return for_view_slices(N, [&](int64_t n0, int64_t n) {
+    return drtk_amd_transform_pinhole_backward(
         dtype, advance(v, n0 * v_sN, es), v_sN, advance(campos, n0 * 3, es), advance(camrot, n0 * 9, es), advance(focal, n0 * 4, es),
-        advance(princpt, n0 * 2, es), advance(grad_v_pix, n0 * V * 3, es), n, V, advance(grad_v, n0 * V * 3, es), stream))
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (dtype) {
-    case DRTK_F32:
-      return transform_backward_impl<float>(static_cast<const float*>(v), v_sN, static_cast<const float*>(campos), static_cast<const float*>(camrot), static_cast<const float*>(focal), static_cast<const float*>(princpt), static_cast<const float*>(grad_v_pix), N, V, static_cast<float*>(grad_v), s);
-    case DRTK_F64:
-      return transform_backward_impl<double>(static_cast<const double*>(v), v_sN, static_cast<const double*>(campos), static_cast<const double*>(camrot), static_cast<const double*>(focal), static_cast<const double*>(princpt), static_cast<const double*>(grad_v_pix), N, V, static_cast<double*>(grad_v), s);
-    default:
-      return DRTK_ERR_INVALID_ARGUMENT;
-  }
+        advance(princpt, n0 * 2, es), advance(grad_v_pix, n0 * V * 3, es), n, V, advance(grad_v, n0 * V * 3, es), stream);
+  });
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return transform_backward_impl<T>(
+        static_cast<const T*>(v), v_sN, static_cast<const T*>(campos), static_cast<const T*>(camrot), static_cast<const T*>(focal),
+        static_cast<const T*>(princpt), static_cast<const T*>(grad_v_pix), N, V, static_cast<T*>(grad_v), static_cast<hipStream_t>(stream));
+  });
 }

@@ -387,9 +387,9 @@ DistortArgs<T> typed(const RawArgs& r) {
 
 // the arguments both directions share; everything is decided on the host, before any launch
 bool valid(drtk_dtype_t dtype, const RawArgs& r) {
-  if (dtype != DRTK_F32 && dtype != DRTK_F64) return false;
+  if (!valid_dtype(dtype)) return false;
   if (r.N < 0 || r.V < 0 || r.V >= (int64_t(1) << 31) || r.N >= (int64_t(1) << 31)) return false;
-  if (r.v_sN != 0 && r.v_sN != r.V * 3) return false;
+  if (bad_view_stride(r.v_sN, r.V * 3)) return false;
   if (r.mode_all < kPinhole || r.mode_all > kFisheye62) return false;
   if (r.ncoef != 4 && r.ncoef != 5 && r.ncoef != 8) return false;
   if (!r.mode_per_view && r.mode_all == kFisheye62 && r.ncoef != 8) return false;
@@ -417,15 +417,14 @@ RawArgs slice(const RawArgs& r, int64_t n0, int64_t n, size_t es) {
 template <typename T>
 int forward_impl(const RawArgs& r, void* v_pix, void* v_cam, hipStream_t stream) {
   const size_t es = sizeof(T);
-  for (int64_t n0 = 0; n0 < r.N; n0 += kMaxViewsPerLaunch) { // the view is blockIdx.y: slices of at most 65 535 views
-    const int64_t n = r.N - n0 < kMaxViewsPerLaunch ? r.N - n0 : kMaxViewsPerLaunch;
+  return for_view_slices(r.N, [&](int64_t n0, int64_t n) { // the view is blockIdx.y: one launch per slice
     const DistortArgs<T> a = typed<T>(slice(r, n0, n, es));
     const dim3 grid(static_cast<unsigned>(ceil_div(r.V, kBlock)), static_cast<unsigned>(n));
     DRTK_LAUNCH((transform_distort_kernel<T>), grid, dim3(kBlock), 0, stream, a,
                 static_cast<T*>(advance(v_pix, n0 * r.V * 3, es)), static_cast<T*>(advance(v_cam, n0 * r.V * 3, es)));
     DRTK_RETURN_IF_LAUNCH_FAILED();
-  }
-  return DRTK_OK;
+    return DRTK_OK;
+  });
 }
 
 template <typename T>
@@ -438,8 +437,7 @@ int backward_impl(const RawArgs& r, const void* grad_v_pix, const void* grad_v_c
     DRTK_RETURN_IF_LAUNCH_FAILED();
     return DRTK_OK;
   }
-  for (int64_t n0 = 0; n0 < r.N; n0 += kMaxViewsPerLaunch) {
-    const int64_t n = r.N - n0 < kMaxViewsPerLaunch ? r.N - n0 : kMaxViewsPerLaunch;
+  return for_view_slices(r.N, [&](int64_t n0, int64_t n) {
     const DistortArgs<T> a = typed<T>(slice(r, n0, n, es));
     const dim3 grid(static_cast<unsigned>(ceil_div(r.V, kBlock)), static_cast<unsigned>(n));
     DRTK_LAUNCH((transform_distort_backward_kernel<T, false>), grid, dim3(kBlock), 0, stream, a,
@@ -447,8 +445,8 @@ int backward_impl(const RawArgs& r, const void* grad_v_pix, const void* grad_v_c
                 static_cast<const T*>(advance(grad_v_cam, n0 * r.V * 3, es)),
                 static_cast<T*>(advance(grad_v, n0 * r.V * 3, es)));
     DRTK_RETURN_IF_LAUNCH_FAILED();
-  }
-  return DRTK_OK;
+    return DRTK_OK;
+  });
 }
 
 } // namespace
@@ -466,8 +464,10 @@ extern "C" int drtk_amd_transform_distort(
   if (!valid(dtype, r)) return DRTK_ERR_INVALID_ARGUMENT;
   if (N * V > 0 && !v_pix) return DRTK_ERR_INVALID_ARGUMENT;
   if (N * V == 0) return DRTK_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return dtype == DRTK_F32 ? forward_impl<float>(r, v_pix, v_cam, s) : forward_impl<double>(r, v_pix, v_cam, s);
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return forward_impl<T>(r, v_pix, v_cam, static_cast<hipStream_t>(stream));
+  });
 }
 
 extern "C" int drtk_amd_transform_distort_backward(
@@ -480,7 +480,8 @@ extern "C" int drtk_amd_transform_distort_backward(
   if (!valid(dtype, r)) return DRTK_ERR_INVALID_ARGUMENT;
   if (N * V > 0 && (!grad_v || (!grad_v_pix && !grad_v_cam))) return DRTK_ERR_INVALID_ARGUMENT;
   if (N * V == 0) return DRTK_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return dtype == DRTK_F32 ? backward_impl<float>(r, grad_v_pix, grad_v_cam, grad_v, s)
-                           : backward_impl<double>(r, grad_v_pix, grad_v_cam, grad_v, s);
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return backward_impl<T>(r, grad_v_pix, grad_v_cam, grad_v, static_cast<hipStream_t>(stream));
+  });
 }

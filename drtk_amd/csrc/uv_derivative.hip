@@ -121,6 +121,20 @@ __global__ __launch_bounds__(kBlock) void uv_derivative_kernel(
 // through the C ABI on the textured benchmark's 2 x 4096^2 pixels -- twice the loads per wave in flight do not make up for
 // half the waves.  Parity was green: fuzz_next_ops 3000.)
 
+// The argument check (tests/test_uv_derivative_args_host.py pins every status): sizes and dtype, then -- only where there is a
+// pixel -- the pointers; the mesh only where there is a triangle, `mask` never.
+int check_uv_derivative_args(
+    drtk_dtype_t dtype, const void* v, int64_t v_sN, const void* vt, int64_t vt_sN, const int32_t* vi, const int32_t* vti,
+    const int32_t* index_img, const void* bary_img, const void* campos, const void* camrot, const void* focal, int64_t N, int64_t V,
+    int64_t T_, int64_t F, int64_t H, int64_t W, const void* out) {
+  if (bad_image(N, H, W) || V < 0 || T_ < 0 || F < 0 || bad_view_stride(v_sN, V * 3) || bad_view_stride(vt_sN, T_ * 2) || !valid_dtype(dtype))
+    return DRTK_ERR_INVALID_ARGUMENT;
+  if (N * H * W == 0) return DRTK_OK;
+  if (!index_img || !bary_img || !out || !campos || !camrot || !focal || (F > 0 && (!vi || !vti || !v || !vt)))
+    return DRTK_ERR_INVALID_ARGUMENT;
+  return DRTK_OK;
+}
+
 } // namespace
 } // namespace drtk_amd
 
@@ -131,34 +145,23 @@ extern "C" int drtk_amd_screen_space_uv_derivative(
     const int32_t* vti, const int32_t* index_img, const void* bary_img, const uint8_t* mask, const void* campos,
     const void* camrot, const void* focal, int64_t N, int64_t V, int64_t T_, int64_t F, int64_t H, int64_t W,
     void* out, drtk_stream_t stream) {
-  if (N < 0 || V < 0 || T_ < 0 || F < 0 || H < 0 || W < 0 || H * W >= (int64_t(1) << 31) ||
-      (v_sN != 0 && v_sN != V * 3) || (vt_sN != 0 && vt_sN != T_ * 2) || (dtype != DRTK_F32 && dtype != DRTK_F64))
-    return DRTK_ERR_INVALID_ARGUMENT;
-  if (N * H * W == 0) return DRTK_OK;
-  if (!index_img || !bary_img || !out || !campos || !camrot || !focal || (F > 0 && (!vi || !vti || !v || !vt)))
-    return DRTK_ERR_INVALID_ARGUMENT;
-  {
-    const size_t es = dtype_size(dtype);
-    DRTK_FOR_VIEW_SLICES(N, n0, n, drtk_amd_screen_space_uv_derivative(
+  const int st = check_uv_derivative_args(dtype, v, v_sN, vt, vt_sN, vi, vti, index_img, bary_img, campos, camrot, focal, N, V, T_, F, H, W, out);
+  if (st != DRTK_OK || N * H * W == 0) return st;
+  const size_t es = dtype_size(dtype);
+  if (N > kMaxViewsPerLaunch) return for_view_slices(N, [&](int64_t n0, int64_t n) {
+    return drtk_amd_screen_space_uv_derivative(
         dtype, advance(v, n0 * v_sN, es), v_sN, advance(vt, n0 * vt_sN, es), vt_sN, vi, vti, advance_typed(index_img, n0 * H * W),
         advance(bary_img, n0 * 3 * H * W, es), advance_typed(mask, n0 * H * W), advance(campos, n0 * 3, es), advance(camrot, n0 * 9, es),
-        advance(focal, n0 * 4, es), n, V, T_, F, H, W, advance(out, n0 * 4 * H * W, es), stream))
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 grid(static_cast<unsigned>(ceil_div(H * W, kBlock)), static_cast<unsigned>(N));
-  if (dtype == DRTK_F32) {
+        advance(focal, n0 * 4, es), n, V, T_, F, H, W, advance(out, n0 * 4 * H * W, es), stream);
+  });
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    const dim3 grid(static_cast<unsigned>(ceil_div(H * W, kBlock)), static_cast<unsigned>(N));
     DRTK_LAUNCH(
-        (uv_derivative_kernel<float>), grid, dim3(kBlock), 0, s, static_cast<const float*>(v), v_sN,
-        static_cast<const float*>(vt), vt_sN, vi, vti, index_img, static_cast<const float*>(bary_img), mask,
-        static_cast<const float*>(campos), static_cast<const float*>(camrot), static_cast<const float*>(focal), H * W,
-        static_cast<float*>(out), xcd_strip(ceil_div(16 * W, kBlock)));
-  } else {
-    DRTK_LAUNCH(
-        (uv_derivative_kernel<double>), grid, dim3(kBlock), 0, s, static_cast<const double*>(v), v_sN,
-        static_cast<const double*>(vt), vt_sN, vi, vti, index_img, static_cast<const double*>(bary_img), mask,
-        static_cast<const double*>(campos), static_cast<const double*>(camrot), static_cast<const double*>(focal),
-        H * W, static_cast<double*>(out), xcd_strip(ceil_div(16 * W, kBlock)));
-  }
-  DRTK_RETURN_IF_LAUNCH_FAILED();
-  return DRTK_OK;
+        (uv_derivative_kernel<T>), grid, dim3(kBlock), 0, static_cast<hipStream_t>(stream), static_cast<const T*>(v), v_sN,
+        static_cast<const T*>(vt), vt_sN, vi, vti, index_img, static_cast<const T*>(bary_img), mask, static_cast<const T*>(campos),
+        static_cast<const T*>(camrot), static_cast<const T*>(focal), H * W, static_cast<T*>(out), xcd_strip(ceil_div(16 * W, kBlock)));
+    DRTK_RETURN_IF_LAUNCH_FAILED();
+    return DRTK_OK;
+  });
 }

@@ -249,6 +249,8 @@ int drtk_amd_edge_grad_backward_fused(
  *   values[pair_indices[n,tri,3i+j]] += bary_i * bary_j over foreground pixels (values zero-filled
  *   here); pair_indices [N,F,9] int32 with batch stride pair_sN (0 = shared).  The CSR pattern itself
  *   (crow / col / pair_indices) is topology-only host work done by the torch shim.
+ * All four judge dtype and sizes first -- an unknown dtype is DRTK_ERR_INVALID_ARGUMENT also where there is nothing to do
+ * (R == 0, nnz == 0, no pixel) -- and every pointer before they write: a rejected call has cleared nothing.
  */
 int drtk_amd_interpolation_matrix(
     drtk_dtype_t dtype, const int32_t* vi, const int32_t* index_img, const void* bary_img,

@@ -1000,3 +1000,37 @@ def test_a_level_beyond_the_32_bit_bound_takes_the_direct_kernel(big_level, mode
         gg_sum += gg1
         del gl1
     close(gg4, gg_sum.cpu(), "grad grid of four channels against the sum of the one-channel calls", atol=2e-5)
+
+
+@pytest.mark.parametrize("dtype", [th.float32, th.float64])
+def test_uv_derivative_more_views_than_one_launch_takes(dtype):
+    """N = 65 537 views of 2 x 2 pixels over a quad of two triangles, per-view vertices and texture coordinates (the view is
+    blockIdx.y: the entry point runs two slices): the first two views and the two either side of the slice boundary equal,
+    bit for bit, those same views run alone."""
+    from drtk_amd import capi
+
+    N, H, W = 65537, 2, 2
+    g = th.Generator(device=DEV).manual_seed(5)
+    rand = lambda *shape: th.rand(*shape, device=DEV, dtype=dtype, generator=g)
+    quad = th.tensor([[-1.0, -1.0], [1.0, -1.0], [1.0, 1.0], [-1.0, 1.0]], device=DEV, dtype=dtype)
+    v = th.cat([quad.expand(N, 4, 2) + 0.1 * rand(N, 4, 2), 3 + rand(N, 4, 1)], -1)
+    vt = (0.5 + 0.4 * quad).expand(N, 4, 2) + 0.02 * rand(N, 4, 2)
+    vi = th.tensor([[0, 1, 2], [0, 2, 3]], device=DEV, dtype=th.int32)
+    index = th.randint(-1, 2, (N, H, W), device=DEV, generator=g).int()
+    bary = rand(N, 3, H, W) + 0.1
+    bary = bary / bary.sum(1, keepdim=True)
+    mask = th.rand(N, H, W, device=DEV, generator=g) < 0.8
+    campos = 0.1 * rand(N, 3)
+    camrot = th.eye(3, device=DEV, dtype=dtype).repeat(N, 1, 1) + 0.05 * rand(N, 3, 3)
+    focal = th.tensor([[500.0, 1.5], [0.0, 480.0]], device=DEV, dtype=dtype).repeat(N, 1, 1) * (0.9 + 0.2 * rand(N, 1, 1))
+    per_view = (v, vt, index, bary, mask, campos, camrot, focal)
+
+    def run(views):
+        a = [t[views].contiguous() for t in per_view]
+        return capi.screen_space_uv_derivative(a[0], a[1], vi, vi, *a[2:])
+
+    jac = run(slice(None))
+    assert jac.shape == (N, H, W, 2, 2) and bool(th.isfinite(jac).all()) and float(jac.abs().max()) > 0
+    assert bool((index[:2] != -1).any()) and bool((index[65535:] != -1).any())
+    for views in (slice(0, 2), slice(65535, 65537)):
+        assert th.equal(run(views), jac[views]), views

@@ -321,3 +321,22 @@ def test_gradcheck_and_double_backward():
     out = drtk_amd.mipmap_pyramid(x)
     with pytest.raises(RuntimeError, match="double backward"):
         th.autograd.grad(sum(t.sum() for t in out), x, create_graph=True)
+
+
+@pytest.mark.parametrize("dtype", [th.float32, th.float64])
+def test_more_views_than_one_launch_takes(dtype):
+    """N = 65 537 views of one 2 x 2 channel, two levels (the view is blockIdx.y: the entry points run two slices), both
+    ways through the C ABI: the first two views and the two either side of the slice boundary equal, bit for bit, those
+    same views run alone."""
+    from drtk_amd import capi
+
+    N = 65537
+    g = th.Generator(device=DEV).manual_seed(11)
+    x = th.rand(N, 1, 2, 2, device=DEV, dtype=dtype, generator=g)
+    grads = [th.rand(N, 1, 2, 2, device=DEV, dtype=dtype, generator=g), th.rand(N, 1, 1, 1, device=DEV, dtype=dtype, generator=g)]
+    level1 = capi.mipmap_pyramid(x, 2)[1]
+    grad_x = capi.mipmap_pyramid_backward(grads)
+    assert level1.shape == (N, 1, 1, 1) and grad_x.shape == x.shape
+    for views in (slice(0, 2), slice(65535, 65537)):
+        assert th.equal(capi.mipmap_pyramid(x[views].contiguous(), 2)[1], level1[views]), views
+        assert th.equal(capi.mipmap_pyramid_backward([t[views].contiguous() for t in grads]), grad_x[views]), views

@@ -1709,3 +1709,59 @@ def test_kernel_timing_brackets_every_launch_and_changes_nothing():
     assert names["fill_bytes_kernel"][0] >= 9
     step()
     assert capi.kernel_timing_report() == {}  # nothing is collected outside begin ... report
+
+
+@pytest.mark.parametrize("dtype", [th.float32, th.float64])
+def test_transform_pinhole_more_views_than_one_launch_takes(dtype):
+    """N = 65 537 views of V = 2 per-view vertices (the view is blockIdx.y: the forward and, with per-view vertices, the
+    backward run two slices): v_pix and the gradient of the first two views and of the two either side of the slice
+    boundary equal, bit for bit, those same views run alone."""
+    from drtk_amd.transform import transform
+
+    N, V = 65537, 2
+    g = th.Generator(device=DEV).manual_seed(3)
+    rand = lambda *shape: th.rand(*shape, device=DEV, dtype=dtype, generator=g)
+    v = th.cat([rand(N, V, 2) * 2 - 1, rand(N, V, 1) + 2], -1)
+    campos = 0.1 * rand(N, 3)
+    camrot = th.eye(3, device=DEV, dtype=dtype).repeat(N, 1, 1) + 0.05 * rand(N, 3, 3)
+    focal = th.tensor([[500.0, 1.5], [0.0, 480.0]], device=DEV, dtype=dtype).repeat(N, 1, 1) * (0.9 + 0.2 * rand(N, 1, 1))
+    princpt = th.tensor([320.0, 240.0], device=DEV, dtype=dtype).repeat(N, 1)
+    grad = rand(N, V, 3) * 2 - 1
+
+    def run(views):
+        vv = v[views].clone().requires_grad_(True)
+        out = transform(vv, campos[views].contiguous(), camrot[views].contiguous(), focal[views].contiguous(), princpt[views].contiguous())
+        out.backward(grad[views].contiguous())
+        return out.detach(), vv.grad
+
+    out, grad_v = run(slice(None))
+    assert out.shape == (N, V, 3) and grad_v.shape == (N, V, 3) and bool(th.isfinite(out).all()) and bool(th.isfinite(grad_v).all())
+    for views in (slice(0, 2), slice(65535, 65537)):
+        out1, grad_v1 = run(views)
+        assert th.equal(out1, out[views]) and th.equal(grad_v1, grad_v[views]), views
+
+
+def test_rejected_sparse_operator_calls_have_written_nothing():
+    """drtk_amd_interpolation_matrix_backward and drtk_amd_interpolation_normal_matrix_values clear their output first
+    thing -- but only once the whole call is accepted: one that is rejected for a missing input leaves the output as it was."""
+    import ctypes
+
+    from drtk_amd import capi
+
+    p, i64 = ctypes.c_void_p, ctypes.c_int64
+    N, F, H, W, R, nnz = 2, 7, 6, 9, 11, 13
+    real = th.zeros(64, device=DEV, dtype=th.int64).data_ptr()  # a valid address for the inputs that are present
+    bary_grad = th.full((N, 3, H, W), 7.0, device=DEV)
+    for missing in range(4):  # grad_values, vi, index_img, row_pixels
+        inputs = [p(0 if k == missing else real) for k in range(4)]
+        st = capi.lib().drtk_amd_interpolation_matrix_backward(
+            ctypes.c_int(capi.DRTK_F32), *inputs, i64(R), i64(N), i64(F), i64(3 * F), i64(H), i64(W), p(bary_grad.data_ptr()), p(0))
+        assert st == -1, missing
+    values = th.full((nnz,), 7.0, device=DEV)
+    for missing in range(3):  # pair_indices, index_img, bary_img
+        inputs = [p(0 if k == missing else real) for k in range(3)]
+        st = capi.lib().drtk_amd_interpolation_normal_matrix_values(
+            ctypes.c_int(capi.DRTK_F32), *inputs, i64(N), i64(F), i64(9 * F), i64(H), i64(W), i64(nnz), p(values.data_ptr()), p(0))
+        assert st == -1, missing
+    th.cuda.synchronize()
+    assert bool((bary_grad == 7).all()) and bool((values == 7).all())
