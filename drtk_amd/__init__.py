@@ -16,9 +16,11 @@ from drtk_amd.filter2d import (  # noqa: F401
     upsample,
 )
 from drtk_amd.geometry import (  # noqa: F401
+    cotangent_weights,
     face_attribute_to_vert,
     face_dpdt,
     face_info,
+    mesh_laplacian,
     vert_binormals,
     vert_normals,
 )
@@ -58,7 +60,9 @@ __version__ = "0.1.0"
 # vert_normals, face_attribute_to_vert, face_dpdt, vert_binormals) is exported here too, and so is `grid_scatter` (the
 # splatting counterpart of grid_sample), `msi` (the multi-sphere-image background) and the eight names of `filter2d` (fused
 # alias-free up/down-sampling and low-pass filtering); the `drtk` drop-in package does not lift these three yet --
-# INTEGRATION.md.  `transform` / `transform_with_v_cam` serve the pinhole camera and, on the HIP device, the reference's
+# INTEGRATION.md.  `cotangent_weights` and `mesh_laplacian` (the mesh regulariser of a geometry fit: cotangent or uniform
+# Laplacian through the cached vertex incidence, one launch each way) are this package's additions too, and stay out of the
+# drop-in (the reference has no such names).  `transform` / `transform_with_v_cam` serve the pinhole camera and, on the HIP device, the reference's
 # distortion models (radial-tangential, fisheye, fisheye62 with its lookup table, per-view lists) in one fused kernel each
 # way; the field-of-view estimators live in drtk_amd.transform (`estimate_rt_fov`, `estimate_fisheye_fov`,
 # `estimate_fisheye62_fov`) and in the drop-in's drtk.utils.  Not provided: the pure-PyTorch `*_ref` models (out of scope).
@@ -99,4 +103,6 @@ __all__ = [
     "face_attribute_to_vert",
     "face_dpdt",
     "vert_binormals",
+    "cotangent_weights",
+    "mesh_laplacian",
 ]

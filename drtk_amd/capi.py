@@ -171,6 +171,11 @@ EXPORTS = [
     "drtk_amd_geometry_face_gather",
     "drtk_amd_geometry_vertex_gather_workspace_bytes",
     "drtk_amd_geometry_vertex_gather",
+    "drtk_amd_geometry_cot_weights",
+    "drtk_amd_geometry_cot_weights_backward",
+    "drtk_amd_geometry_laplacian_workspace_bytes",
+    "drtk_amd_geometry_laplacian",
+    "drtk_amd_geometry_laplacian_grad_weights",
     "drtk_amd_selftest_exact_div",
     "drtk_amd_kernel_timing_begin",
     "drtk_amd_kernel_timing_report",
@@ -1099,6 +1104,93 @@ def geometry_vertex_gather(src, incidence, num_vertices, per_corner=False, norma
             _p(sums), _p(ws), ctypes.c_size_t(need.value), _stream(src, stream)),
         "geometry_vertex_gather")
     return out, sums
+
+
+@_on_tensor_device
+def geometry_cot_weights(v, vi, stream=None):
+    """Cotangent weights [N,F,3] of v [N,V,3] over int32 vi [F,3] / [N,F,3]: cot(angle at corner k) / 2, the weight of the
+    edge opposite corner k; 0 for a face whose |c| > 0 is false."""
+    v = v.contiguous()
+    N, V = v.shape[0], v.shape[1]
+    vi_c, vi_sN, _ = _geometry_topology(vi)
+    F = vi_c.shape[-2]
+    w = _out(N, F, 3, dtype=v.dtype, device=v.device)
+    _check(lib().drtk_amd_geometry_cot_weights(ctypes.c_int(_dt(v)), _p(v), _i(V * 3), _p(vi_c), _i(vi_sN), _i(N), _i(V),
+                                               _i(F), _p(w), _stream(v, stream)), "geometry_cot_weights")
+    return w
+
+
+@_on_tensor_device
+def geometry_cot_weights_backward(v, vi, grad_weights, stream=None):
+    """Per-corner rows [N,F,3,3] of grad_v from grad_weights [N,F,3]; reduce with geometry_vertex_gather(per_corner=True)."""
+    v = v.contiguous()
+    N, V = v.shape[0], v.shape[1]
+    vi_c, vi_sN, _ = _geometry_topology(vi)
+    F = vi_c.shape[-2]
+    g = grad_weights.contiguous()
+    assert g.shape == (N, F, 3) and g.dtype == v.dtype
+    pos = _out(N, F, 3, 3, dtype=v.dtype, device=v.device)
+    _check(lib().drtk_amd_geometry_cot_weights_backward(ctypes.c_int(_dt(v)), _p(v), _i(V * 3), _p(vi_c), _i(vi_sN), _i(N),
+                                                        _i(V), _i(F), _p(g), _p(pos), _stream(v, stream)),
+           "geometry_cot_weights_backward")
+    return pos
+
+
+def _laplacian_weights(weights, x, F):
+    """weights None / [F,3] / [1,F,3] / [N,F,3] -> (contiguous tensor or None, view stride in elements, B)"""
+    if weights is None:
+        return None, 0, 1
+    w = weights.contiguous()
+    assert w.dtype == x.dtype and w.shape[-2:] == (F, 3)
+    if w.ndim == 2 or w.shape[0] == 1:
+        return w, 0, 1
+    assert w.shape[0] == x.shape[0]
+    return w, F * 3, w.shape[0]
+
+
+@_on_tensor_device
+def geometry_laplacian(x, vi, incidence, weights=None, stream=None):
+    """out [N,V,C] = sum_j w_ij (x_j - x_i) of x [N,V,C] over int32 vi [F,3] / [N,F,3] and its incidence
+    (vertex_incidence_numpy(vi, V), device tensors or numpy arrays); weights [F,3] / [1,F,3] / [N,F,3], or None: every
+    face edge weighs 1/2."""
+    x = x.contiguous()
+    N, V, C = x.shape
+    vi_c, vi_sN, B = _geometry_topology(vi)
+    F = vi_c.shape[-2]
+    inc = [th.as_tensor(a, dtype=th.int32, device=x.device).contiguous() for a in incidence]
+    crow, entries, chunk_ptr, chunk_begin, chunk_row = inc
+    assert crow.numel() == B * V + 1
+    nch = chunk_row.numel()
+    w, w_sN, _ = _laplacian_weights(weights, x, F)
+    out = _out(N, V, C, dtype=x.dtype, device=x.device)
+    need = ctypes.c_size_t(0)
+    _check(lib().drtk_amd_geometry_laplacian_workspace_bytes(ctypes.c_int(_dt(x)), _i(N), _i(B), _i(nch), _i(C),
+                                                             ctypes.byref(need)), "geometry_laplacian")
+    ws = _out(max(need.value, 1), dtype=th.uint8, device=x.device)
+    _check(
+        lib().drtk_amd_geometry_laplacian(
+            ctypes.c_int(_dt(x)), _p(x), _i(C), _p(vi_c), _i(vi_sN), _p(w), _i(w_sN), _p(crow), _p(entries),
+            _p(chunk_ptr if nch else None), _p(chunk_begin if nch else None), _p(chunk_row if nch else None), _i(nch),
+            _i(B), _i(N), _i(V), _i(F), _p(out), _p(ws), ctypes.c_size_t(need.value), _stream(x, stream)),
+        "geometry_laplacian")
+    return out
+
+
+@_on_tensor_device
+def geometry_laplacian_grad_weights(grad_out, x, vi, shared_weights=False, stream=None):
+    """grad_weights [N,F,3] (shared_weights: [1,F,3], summed over the views in ascending order) of geometry_laplacian."""
+    x = x.contiguous()
+    g = grad_out.contiguous()
+    assert g.shape == x.shape and g.dtype == x.dtype
+    N, V, C = x.shape
+    vi_c, vi_sN, _ = _geometry_topology(vi)
+    F = vi_c.shape[-2]
+    wB = 1 if shared_weights else N
+    gw = _out(wB, F, 3, dtype=x.dtype, device=x.device)
+    _check(lib().drtk_amd_geometry_laplacian_grad_weights(ctypes.c_int(_dt(x)), _p(g), _p(x), _i(C), _p(vi_c), _i(vi_sN),
+                                                          _i(N), _i(V), _i(F), _i(wB), _p(gw), _stream(x, stream)),
+           "geometry_laplacian_grad_weights")
+    return gw
 
 
 def edge_grad_backward_workspace_bytes(dtype, N, H, W) -> int:

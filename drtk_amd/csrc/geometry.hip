@@ -14,6 +14,11 @@
 // Rows longer than DRTK_GEOMETRY_CHUNK entries are split into chunks of that length: one lane per (view, chunk) sums a
 // chunk, and the vertex pass adds the chunk sums in chunk order.  Every sum has one fixed order, so results are
 // bitwise reproducible and independent of the launch shape.
+//
+// The mesh regulariser rides on the same structure: cotangent weights are a face pass each way (backward: per-corner
+// rows, reduced by the vertex pass), and the weighted graph Laplacian sum_j w_ij (x_j - x_i) is a vertex pass that
+// walks the incidence row and reads the face's indices and weights per entry -- no vertex-vertex adjacency, nothing
+// padded; it is symmetric, so its backward with respect to x is itself, and the weights' gradient is a face pass.
 #include "common.hpp"
 
 namespace drtk_amd {
@@ -369,6 +374,213 @@ __global__ __launch_bounds__(kBlock) void geom_vertex_gather_kernel(
   }
 }
 
+// ---- cotangent weights and the mesh Laplacian ---------------------------------------------------------------------
+// w[n,f,k] = dot(p_{k+1} - p_k, p_{k+2} - p_k) / (2 |c|) = cot(angle at corner k) / 2, c of the face pass; exactly 0 for
+// all three k where |c| > 0 is false (c zero: duplicate or collinear corners; c NaN).
+template <typename T>
+__global__ __launch_bounds__(kBlock) void cot_weights_face_kernel(
+    const T* __restrict__ v, int64_t v_sN, const int32_t* __restrict__ vi, int64_t vi_sN, int64_t N, int64_t F,
+    T* __restrict__ w) {
+  const int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x;
+  if (i >= N * F) return;
+  const int64_t n = i / F, f = i - n * F;
+  T p[3][3];
+  load_corners(v + n * v_sN, vi + n * vi_sN + f * 3, p);
+  T a[3], b[3], c[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) a[j] = p[0][j] - p[2][j], b[j] = p[1][j] - p[0][j];
+  cross3(a, b, c);
+  const T nrm = norm3(c);
+  const bool ok = nrm > T(0);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const int k1 = (k + 1) % 3, k2 = (k + 2) % 3;
+    T d = T(0);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) d += (p[k1][j] - p[k][j]) * (p[k2][j] - p[k][j]);
+    w[i * 3 + k] = ok ? d / (T(2) * nrm) : T(0);
+  }
+}
+
+// Backward of the above: the per-corner rows [N,F,3,3] of grad_v from g_w [N,F,3]; a face whose weights are the
+// degenerate zeros gives zero rows.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void cot_weights_face_backward_kernel(
+    const T* __restrict__ v, int64_t v_sN, const int32_t* __restrict__ vi, int64_t vi_sN, int64_t N, int64_t F,
+    const T* __restrict__ g_w, T* __restrict__ pos_rows) {
+  const int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x;
+  if (i >= N * F) return;
+  const int64_t n = i / F, f = i - n * F;
+  T p[3][3];
+  load_corners(v + n * v_sN, vi + n * vi_sN + f * 3, p);
+  T a[3], b[3], c[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) a[j] = p[0][j] - p[2][j], b[j] = p[1][j] - p[0][j];
+  cross3(a, b, c);
+  const T nrm = norm3(c);
+  T gp[3][3] = {{T(0), T(0), T(0)}, {T(0), T(0), T(0)}, {T(0), T(0), T(0)}};
+  if (nrm > T(0)) {
+    const T two_nrm = T(2) * nrm;
+    T gn = T(0); // gradient of |c|:  w_k = d_k / (2 |c|)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const int k1 = (k + 1) % 3, k2 = (k + 2) % 3;
+      T e1[3], e2[3], d = T(0);
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        e1[j] = p[k1][j] - p[k][j], e2[j] = p[k2][j] - p[k][j];
+        d += e1[j] * e2[j];
+      }
+      const T g = g_w[i * 3 + k];
+      const T gd = g / two_nrm;
+      gn -= (g * d) / (two_nrm * nrm);
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        gp[k1][j] += gd * e2[j];
+        gp[k2][j] += gd * e1[j];
+        gp[k][j] -= gd * (e1[j] + e2[j]);
+      }
+    }
+    // |c| -> c = a x b:  gc = gn c / |c|, ga = b x gc, gb = gc x a;  a = p0 - p2, b = p1 - p0
+    T gc[3], ga[3], gb[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) gc[j] = gn * (c[j] / nrm);
+    cross3(b, gc, ga);
+    cross3(gc, a, gb);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      gp[0][j] += ga[j] - gb[j];
+      gp[1][j] += gb[j];
+      gp[2][j] -= ga[j];
+    }
+  }
+  T* o = pos_rows + i * 9;
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) o[k * 3 + j] = gp[k][j];
+}
+
+// The entries [beg, end) of vertex i's incidence row, channels c0 .. c0+3 of C: per entry (f, k), i = a_k, the bracket
+//   w[f,k+1] * (x[a_{k+2}] - x[i]) + w[f,k+2] * (x[a_{k+1}] - x[i])
+// evaluated as written and then added to acc, in entry order.  x, vi, w: the view's.  WEIGHTED false: every w is 1/2 and
+// w is not read.
+template <typename T, bool WEIGHTED>
+__device__ __forceinline__ void laplacian_entries(
+    const T* __restrict__ x, const int32_t* __restrict__ vi, const T* __restrict__ w,
+    const int32_t* __restrict__ entries, int32_t beg, int32_t end, const T xi[4], int64_t C, int64_t c0, T acc[4]) {
+#pragma unroll 2
+  for (int32_t j = beg; j < end; ++j) {
+    const int32_t e = entries[j];
+    const int32_t f = e / 3, k = e - f * 3;
+    const int k1 = k == 2 ? 0 : k + 1, k2 = k == 0 ? 2 : k - 1;
+    const int64_t f3 = int64_t(f) * 3;
+    const T* x1 = x + int64_t(vi[f3 + k1]) * C + c0;
+    const T* x2 = x + int64_t(vi[f3 + k2]) * C + c0;
+    const T w1 = WEIGHTED ? w[f3 + k1] : T(0.5);
+    const T w2 = WEIGHTED ? w[f3 + k2] : T(0.5);
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if (c0 + q < C) acc[q] += w1 * (x2[q] - xi[q]) + w2 * (x1[q] - xi[q]);
+  }
+}
+
+// One chunk of a long incidence row: lane per (replica, chunk); replica = view when the topology is shared.
+template <typename T, bool WEIGHTED>
+__global__ __launch_bounds__(kBlock) void laplacian_chunk_kernel(
+    const T* __restrict__ x, int64_t C, const int32_t* __restrict__ vi, int64_t vi_sN, const T* __restrict__ w,
+    int64_t w_sN, const int32_t* __restrict__ crow, const int32_t* __restrict__ entries,
+    const int32_t* __restrict__ chunk_begin, const int32_t* __restrict__ chunk_row, int64_t num_chunks, int64_t reps,
+    int64_t V, bool shared, T* __restrict__ partial) {
+  const int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x;
+  if (i >= reps * num_chunks) return;
+  const int64_t rep = i / num_chunks, c = i - rep * num_chunks;
+  const int64_t r = chunk_row[c];
+  const int64_t b = r / V, vert = r - b * V;
+  const int64_t n = shared ? rep : b;
+  const int32_t beg = chunk_begin[c];
+  const int32_t end = min(beg + kChunk, crow[r + 1]);
+  const T* xn = x + n * V * C;
+  for (int64_t c0 = 0; c0 < C; c0 += 4) {
+    T xi[4], acc[4] = {T(0), T(0), T(0), T(0)};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) xi[q] = c0 + q < C ? xn[vert * C + c0 + q] : T(0);
+    laplacian_entries<T, WEIGHTED>(xn, vi + n * vi_sN, WEIGHTED ? w + n * w_sN : nullptr, entries, beg, end, xi, C, c0, acc);
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if (c0 + q < C) partial[i * C + c0 + q] = acc[q];
+  }
+}
+
+// out[n,i,:] = sum_j w_ij (x_j - x_i): lane per (view, vertex) over its incidence row in CSR order; a long row: its
+// chunk sums in chunk order.
+template <typename T, bool WEIGHTED>
+__global__ __launch_bounds__(kBlock) void laplacian_vertex_kernel(
+    const T* __restrict__ x, int64_t C, const int32_t* __restrict__ vi, int64_t vi_sN, const T* __restrict__ w,
+    int64_t w_sN, const int32_t* __restrict__ crow, const int32_t* __restrict__ entries,
+    const int32_t* __restrict__ chunk_ptr, const T* __restrict__ partial, int64_t num_chunks, bool shared, int64_t N,
+    int64_t V, T* __restrict__ out) {
+  const int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x;
+  if (i >= N * V) return;
+  const int64_t n = i / V, vert = i - n * V;
+  const int64_t r = (shared ? 0 : n * V) + vert;
+  const int32_t c0_ = chunk_ptr ? chunk_ptr[r] : 0, c1_ = chunk_ptr ? chunk_ptr[r + 1] : 0;
+  const int32_t beg = crow[r], end = crow[r + 1];
+  const T* xn = x + n * V * C;
+  for (int64_t c0 = 0; c0 < C; c0 += 4) {
+    T acc[4] = {T(0), T(0), T(0), T(0)};
+    if (c1_ > c0_) {
+      const T* part = partial + (shared ? n * num_chunks : 0) * C + c0;
+      for (int32_t c = c0_; c < c1_; ++c) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          if (c0 + q < C) acc[q] += part[int64_t(c) * C + q];
+      }
+    } else {
+      T xi[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) xi[q] = c0 + q < C ? xn[vert * C + c0 + q] : T(0);
+      laplacian_entries<T, WEIGHTED>(xn, vi + n * vi_sN, WEIGHTED ? w + n * w_sN : nullptr, entries, beg, end, xi, C, c0, acc);
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if (c0 + q < C) out[i * C + c0 + q] = acc[q];
+  }
+}
+
+// grad_w[n,f,k] = -dot(g[a_{k+1}] - g[a_{k+2}], x[a_{k+1}] - x[a_{k+2}]) over the channels, ascending; shared weights:
+// lane per face, the views' dots subtracted from 0 in ascending n.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void laplacian_grad_weights_kernel(
+    const T* __restrict__ g, const T* __restrict__ x, int64_t C, const int32_t* __restrict__ vi, int64_t vi_sN,
+    int64_t N, int64_t V, int64_t F, bool shared_w, T* __restrict__ grad_w) {
+  const int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x;
+  if (i >= (shared_w ? 1 : N) * F) return;
+  const int64_t nw = i / F, f = i - nw * F;
+  const int64_t n0 = shared_w ? 0 : nw, n1 = shared_w ? N : nw + 1;
+  T acc[3] = {T(0), T(0), T(0)};
+  for (int64_t n = n0; n < n1; ++n) {
+    const int32_t* fi = vi + n * vi_sN + f * 3;
+    const T* gn = g + n * V * C;
+    const T* xn = x + n * V * C;
+    const int64_t a[3] = {int64_t(fi[0]) * C, int64_t(fi[1]) * C, int64_t(fi[2]) * C};
+    T d[3] = {T(0), T(0), T(0)};
+    for (int64_t c = 0; c < C; ++c) {
+      const T gv[3] = {gn[a[0] + c], gn[a[1] + c], gn[a[2] + c]};
+      const T xv[3] = {xn[a[0] + c], xn[a[1] + c], xn[a[2] + c]};
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const int k1 = (k + 1) % 3, k2 = (k + 2) % 3;
+        d[k] += (gv[k1] - gv[k2]) * (xv[k1] - xv[k2]);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) acc[k] -= d[k];
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) grad_w[i * 3 + k] = acc[k];
+}
+
 inline dim3 grid_1d(int64_t items) {
   return dim3(static_cast<unsigned>(ceil_div(items, kBlock)));
 }
@@ -441,6 +653,27 @@ int vertex_gather_impl(const void* src, int64_t src_sN, int per_corner, int64_t 
                 src_sN, per_corner, A, crow, entries, C > 0 ? chunk_ptr : nullptr, partial, C, shared, N, V,
                 static_cast<T*>(out), static_cast<T*>(sums));
   }
+  DRTK_RETURN_IF_LAUNCH_FAILED();
+  return DRTK_OK;
+}
+
+template <typename T, bool WEIGHTED>
+int laplacian_impl(const void* x, int64_t C, const int32_t* vi, int64_t vi_sN, const void* w, int64_t w_sN,
+                   const int32_t* crow, const int32_t* entries, const int32_t* chunk_ptr, const int32_t* chunk_begin,
+                   const int32_t* chunk_row, int64_t num_chunks, int64_t B, int64_t N, int64_t V, void* out,
+                   void* workspace, hipStream_t s) {
+  const bool shared = B == 1;
+  T* partial = static_cast<T*>(workspace);
+  if (num_chunks > 0) {
+    const int64_t reps = shared ? N : 1;
+    DRTK_LAUNCH((laplacian_chunk_kernel<T, WEIGHTED>), grid_1d(reps * num_chunks), dim3(kBlock), 0, s,
+                static_cast<const T*>(x), C, vi, vi_sN, static_cast<const T*>(w), w_sN, crow, entries, chunk_begin,
+                chunk_row, num_chunks, reps, V, shared, partial);
+    DRTK_RETURN_IF_LAUNCH_FAILED();
+  }
+  DRTK_LAUNCH((laplacian_vertex_kernel<T, WEIGHTED>), grid_1d(N * V), dim3(kBlock), 0, s, static_cast<const T*>(x), C,
+              vi, vi_sN, static_cast<const T*>(w), w_sN, crow, entries, num_chunks > 0 ? chunk_ptr : nullptr, partial,
+              num_chunks, shared, N, V, static_cast<T*>(out));
   DRTK_RETURN_IF_LAUNCH_FAILED();
   return DRTK_OK;
 }
@@ -541,5 +774,88 @@ extern "C" int drtk_amd_geometry_vertex_gather(
     return vertex_gather_impl<T>(
         src, src_sN, per_corner, A, crow, entries, chunk_ptr, chunk_begin, chunk_row, num_chunks, B, N, V, out, vert_sums, normalize,
         workspace, static_cast<hipStream_t>(stream));
+  });
+}
+
+extern "C" int drtk_amd_geometry_cot_weights(
+    drtk_dtype_t dtype, const void* v, int64_t v_sN, const int32_t* vi, int64_t vi_sN, int64_t N, int64_t V, int64_t F,
+    void* weights, drtk_stream_t stream) {
+  if (!valid_dtype(dtype)) return DRTK_ERR_INVALID_ARGUMENT;
+  if (bad_sizes(N, V, F) || bad_view_stride(v_sN, V * 3) || bad_view_stride(vi_sN, F * 3)) return DRTK_ERR_INVALID_ARGUMENT;
+  if (N * F == 0) return DRTK_OK;
+  if (!v || !vi || !weights || V == 0) return DRTK_ERR_INVALID_ARGUMENT;
+  return dispatch_dtype(dtype, [&](auto tag) -> int {
+    using T = decltype(tag);
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    DRTK_LAUNCH((cot_weights_face_kernel<T>), grid_1d(N * F), dim3(kBlock), 0, s, static_cast<const T*>(v), v_sN, vi, vi_sN, N, F, static_cast<T*>(weights));
+    DRTK_RETURN_IF_LAUNCH_FAILED();
+    return DRTK_OK;
+  });
+}
+
+extern "C" int drtk_amd_geometry_cot_weights_backward(
+    drtk_dtype_t dtype, const void* v, int64_t v_sN, const int32_t* vi, int64_t vi_sN, int64_t N, int64_t V, int64_t F,
+    const void* grad_weights, void* pos_rows, drtk_stream_t stream) {
+  if (!valid_dtype(dtype)) return DRTK_ERR_INVALID_ARGUMENT;
+  if (bad_sizes(N, V, F) || bad_view_stride(v_sN, V * 3) || bad_view_stride(vi_sN, F * 3)) return DRTK_ERR_INVALID_ARGUMENT;
+  if (N * F == 0) return DRTK_OK;
+  if (!v || !vi || !grad_weights || !pos_rows || V == 0) return DRTK_ERR_INVALID_ARGUMENT;
+  return dispatch_dtype(dtype, [&](auto tag) -> int {
+    using T = decltype(tag);
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    DRTK_LAUNCH((cot_weights_face_backward_kernel<T>), grid_1d(N * F), dim3(kBlock), 0, s, static_cast<const T*>(v), v_sN, vi, vi_sN, N, F, static_cast<const T*>(grad_weights), static_cast<T*>(pos_rows));
+    DRTK_RETURN_IF_LAUNCH_FAILED();
+    return DRTK_OK;
+  });
+}
+
+extern "C" int drtk_amd_geometry_laplacian_workspace_bytes(
+    drtk_dtype_t dtype, int64_t N, int64_t B, int64_t num_chunks, int64_t C, size_t* bytes) {
+  return drtk_amd_geometry_vertex_gather_workspace_bytes(dtype, N, B, num_chunks, C, bytes); // one partial row per (replica, chunk)
+}
+
+extern "C" int drtk_amd_geometry_laplacian(
+    drtk_dtype_t dtype, const void* x, int64_t C, const int32_t* vi, int64_t vi_sN, const void* weights, int64_t w_sN,
+    const int32_t* crow, const int32_t* entries, const int32_t* chunk_ptr, const int32_t* chunk_begin,
+    const int32_t* chunk_row, int64_t num_chunks, int64_t B, int64_t N, int64_t V, int64_t F, void* out, void* workspace,
+    size_t workspace_bytes, drtk_stream_t stream) {
+  if (!valid_dtype(dtype)) return DRTK_ERR_INVALID_ARGUMENT;
+  if (bad_sizes(N, V, F) || C < 1 || num_chunks < 0 || (B != 1 && B != N)) return DRTK_ERR_INVALID_ARGUMENT;
+  // the topology the incidence was built from: shared (B = 1, stride 0) or one per view
+  if (bad_view_stride(vi_sN, F * 3) || (N > 1 && (vi_sN != 0) != (B == N))) return DRTK_ERR_INVALID_ARGUMENT;
+  if (bad_view_stride(w_sN, F * 3) || (!weights && w_sN != 0)) return DRTK_ERR_INVALID_ARGUMENT;
+  if (N > 0 && (num_chunks > kMaxLanes / N || 3 * F * B >= (int64_t(1) << 31))) return DRTK_ERR_INVALID_ARGUMENT;
+  if (N * V == 0) return DRTK_OK;
+  if (!x || !crow || !out || (F > 0 && (!vi || !entries))) return DRTK_ERR_INVALID_ARGUMENT;
+  if (num_chunks > 0) {
+    if (!chunk_ptr || !chunk_begin || !chunk_row) return DRTK_ERR_INVALID_ARGUMENT;
+    size_t need = 0;
+    drtk_amd_geometry_laplacian_workspace_bytes(dtype, N, B, num_chunks, C, &need);
+    if (!workspace || workspace_bytes < need) return DRTK_ERR_WORKSPACE_TOO_SMALL;
+  }
+  return dispatch_dtype(dtype, [&](auto tag) -> int {
+    using T = decltype(tag);
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    if (weights)
+      return laplacian_impl<T, true>(x, C, vi, vi_sN, weights, w_sN, crow, entries, chunk_ptr, chunk_begin, chunk_row, num_chunks, B, N, V, out, workspace, s);
+    return laplacian_impl<T, false>(x, C, vi, vi_sN, nullptr, 0, crow, entries, chunk_ptr, chunk_begin, chunk_row, num_chunks, B, N, V, out, workspace, s);
+  });
+}
+
+extern "C" int drtk_amd_geometry_laplacian_grad_weights(
+    drtk_dtype_t dtype, const void* grad_out, const void* x, int64_t C, const int32_t* vi, int64_t vi_sN, int64_t N,
+    int64_t V, int64_t F, int64_t weights_B, void* grad_weights, drtk_stream_t stream) {
+  if (!valid_dtype(dtype)) return DRTK_ERR_INVALID_ARGUMENT;
+  if (bad_sizes(N, V, F) || C < 1 || bad_view_stride(vi_sN, F * 3) || (weights_B != 1 && weights_B != N))
+    return DRTK_ERR_INVALID_ARGUMENT;
+  if (weights_B * F == 0) return DRTK_OK;
+  if (!vi || !grad_weights || (N > 0 && (!grad_out || !x || V == 0))) return DRTK_ERR_INVALID_ARGUMENT;
+  const bool shared_w = weights_B == 1; // (N = 0 with shared weights: the empty sum, zeros)
+  return dispatch_dtype(dtype, [&](auto tag) -> int {
+    using T = decltype(tag);
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    DRTK_LAUNCH((laplacian_grad_weights_kernel<T>), grid_1d(weights_B * F), dim3(kBlock), 0, s, static_cast<const T*>(grad_out), static_cast<const T*>(x), C, vi, vi_sN, N, V, F, shared_w, static_cast<T*>(grad_weights));
+    DRTK_RETURN_IF_LAUNCH_FAILED();
+    return DRTK_OK;
   });
 }

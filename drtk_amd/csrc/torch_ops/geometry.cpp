@@ -1,6 +1,7 @@
 // drtk_amd_ext mesh-geometry operators -- drtk/utils/geometry.py of the reference (face_info, vert_normals,
 // face_attribute_to_vert, face_dpdt, vert_binormals) over drtk_amd_geometry_* (csrc/geometry.hip): a face pass and a
 // vertex pass that sums through the vertex incidence, each way, without float atomics.
+// Also this package's mesh regulariser on the same passes: cotangent_weights and mesh_laplacian.
 #include "common.hpp"
 
 #include <hip/hip_runtime_api.h>
@@ -595,6 +596,158 @@ Tensor vert_binormals_autograd(const Tensor& v, const Tensor& vt, const Tensor& 
 }
 
 // ---------------------------------------------------------------------------------------------
+// cotangent_weights and mesh_laplacian (the mesh regulariser; no counterpart in the reference's library)
+// ---------------------------------------------------------------------------------------------
+Tensor cot_weights_forward(const Tensor& v, const Incidence& inc) {
+  const int64_t N = v.size(0);
+  auto w = out_empty({N, inc.F, 3}, v.options());
+  check_status(drtk_amd_geometry_cot_weights(dtype_of(v, "cotangent_weights"), v.data_ptr(), v.size(1) * 3,
+                                             inc.vi32.data_ptr<int32_t>(), vi_stride(inc), N, v.size(1), inc.F,
+                                             w.data_ptr(), current_stream(v)),
+               "cotangent_weights");
+  return w;
+}
+
+Tensor cotangent_weights_hip(const Tensor& v_, const Tensor& vi) {
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(v_.device());
+  const Tensor v = prep_v(v_, "cotangent_weights");
+  return cot_weights_forward(v, incidence_of(vi, v.size(0), v.size(1), "cotangent_weights"));
+}
+
+class CotangentWeightsFunction : public torch::autograd::Function<CotangentWeightsFunction> {
+ public:
+  static tensor_list forward(AutogradContext* ctx, const Tensor& v_, const Tensor& vi) {
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(v_.device());
+    ctx->set_materialize_grads(false);
+    const Tensor v = prep_v(v_, "cotangent_weights");
+    const Incidence inc = incidence_of(vi, v.size(0), v.size(1), "cotangent_weights");
+    ctx->save_for_backward({v});
+    save_requires_grad(ctx, v_, Tensor());
+    save_incidence(ctx, "", inc);
+    at::AutoDispatchBelowADInplaceOrView g;
+    return {cot_weights_forward(v, inc)};
+  }
+  static tensor_list backward(AutogradContext* ctx, tensor_list go) {
+    const Tensor v = ctx->get_saved_variables()[0];
+    if (!go[0].defined() || !wants(ctx, "v_requires_grad")) return {Tensor(), Tensor()};
+    no_double_backward("cotangent_weights_backward");
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(v.device());
+    const Incidence inc = load_incidence(ctx, "");
+    const Tensor gw = grad_or_undef(go[0], v);
+    const int64_t N = v.size(0);
+    auto pos = out_empty({N, inc.F, 3, 3}, v.options());
+    check_status(drtk_amd_geometry_cot_weights_backward(
+                     dtype_of(v, "cotangent_weights_backward"), v.data_ptr(), v.size(1) * 3,
+                     inc.vi32.data_ptr<int32_t>(), vi_stride(inc), N, v.size(1), inc.F, gw.data_ptr(), pos.data_ptr(),
+                     current_stream(v)),
+                 "cotangent_weights_backward");
+    return {vertex_gather(pos, true, 3, inc, N, false, nullptr, "cotangent_weights_backward"), Tensor()};
+  }
+};
+Tensor cotangent_weights_autograd(const Tensor& v, const Tensor& vi) {
+  return CotangentWeightsFunction::apply(v, vi)[0];
+}
+
+// x [N,V,C] and the weights the kernels read: undefined (uniform), or [B,F,3] contiguous in x's dtype with B = 1 or N
+// (a stride-0 expand counts as 1)
+struct LaplacianArgs {
+  Tensor x, w;
+  Incidence inc;
+};
+LaplacianArgs laplacian_prep(const Tensor& x_, const Tensor& vi, const c10::optional<Tensor>& weights) {
+  const char* op = "mesh_laplacian";
+  LaplacianArgs a;
+  TORCH_CHECK(x_.is_cuda(), op, "(): drtk_amd implements the MI355X (HIP) path only; got CPU tensors");
+  TORCH_CHECK(x_.dim() == 3 && x_.size(2) >= 1, op, "(): expected x of shape [N, V, C] with C >= 1");
+  dtype_of(x_, op);
+  a.x = x_.contiguous();
+  const int64_t N = a.x.size(0);
+  a.inc = incidence_of(vi, N, a.x.size(1), op);
+  if (weights.has_value() && weights->defined()) {
+    Tensor w = weights->dim() == 2 ? weights->unsqueeze(0) : *weights;
+    TORCH_CHECK(w.dim() == 3 && w.size(1) == a.inc.F && w.size(2) == 3 && (w.size(0) == 1 || w.size(0) == N), op,
+                "(): expected weights of shape [F, 3], [1, F, 3] or [N, F, 3]");
+    if (w.size(0) > 1 && w.stride(0) == 0) w = w.narrow(0, 0, 1);
+    a.w = like_v(w, a.x, op, "weights");
+  }
+  return a;
+}
+
+Tensor laplacian_apply(const Tensor& x, const Tensor& w, const Incidence& inc, const char* op) {
+  const drtk_dtype_t dt = dtype_of(x, op);
+  const int64_t N = x.size(0), C = x.size(2);
+  auto out = out_empty({N, inc.V, C}, x.options());
+  size_t bytes = 0;
+  check_status(drtk_amd_geometry_laplacian_workspace_bytes(dt, N, inc.B, inc.C, C, &bytes), op);
+  Tensor ws = bytes ? alloc_workspace(bytes, x) : Tensor();
+  const bool chunks = inc.C > 0;
+  check_status(
+      drtk_amd_geometry_laplacian(
+          dt, x.data_ptr(), C, inc.vi32.data_ptr<int32_t>(), vi_stride(inc), ptr_or_null(w),
+          w.defined() && w.size(0) > 1 ? inc.F * 3 : 0, inc.crow.data_ptr<int32_t>(), inc.entries.data_ptr<int32_t>(),
+          chunks ? inc.chunk_ptr.data_ptr<int32_t>() : nullptr, chunks ? inc.chunk_begin.data_ptr<int32_t>() : nullptr,
+          chunks ? inc.chunk_row.data_ptr<int32_t>() : nullptr, inc.C, inc.B, N, inc.V, inc.F, out.data_ptr(),
+          ws.defined() ? ws.data_ptr() : nullptr, bytes, current_stream(x)),
+      op);
+  return out;
+}
+
+Tensor mesh_laplacian_hip(const Tensor& x, const Tensor& vi, const c10::optional<Tensor>& weights) {
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  const LaplacianArgs a = laplacian_prep(x, vi, weights);
+  return laplacian_apply(a.x, a.w, a.inc, "mesh_laplacian");
+}
+
+class MeshLaplacianFunction : public torch::autograd::Function<MeshLaplacianFunction> {
+ public:
+  static tensor_list forward(AutogradContext* ctx, const Tensor& x, const Tensor& vi,
+                             const c10::optional<Tensor>& weights) {
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+    ctx->set_materialize_grads(false);
+    const LaplacianArgs a = laplacian_prep(x, vi, weights);
+    const bool has_w = a.w.defined();
+    const bool need_w = has_w && weights->requires_grad();
+    ctx->save_for_backward({need_w ? a.x : Tensor(), a.w});
+    ctx->saved_data["x_requires_grad"] = x.requires_grad();
+    ctx->saved_data["w_requires_grad"] = need_w;
+    if (has_w) {
+      // the gradient takes the shape and dtype of the weights as they were passed (an expanded [N,F,3] gets per-view rows)
+      ctx->saved_data["w_sizes"] = weights->sizes().vec();
+      ctx->saved_data["w_dtype"] = static_cast<int64_t>(weights->scalar_type());
+    }
+    save_incidence(ctx, "", a.inc);
+    at::AutoDispatchBelowADInplaceOrView g;
+    return {laplacian_apply(a.x, a.w, a.inc, "mesh_laplacian")};
+  }
+  static tensor_list backward(AutogradContext* ctx, tensor_list go) {
+    const bool need_x = ctx->saved_data["x_requires_grad"].toBool(), need_w = ctx->saved_data["w_requires_grad"].toBool();
+    if (!go[0].defined() || !(need_x || need_w)) return {Tensor(), Tensor(), Tensor()};
+    no_double_backward("mesh_laplacian_backward");
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(go[0].device());
+    const auto saved = ctx->get_saved_variables();
+    const Tensor &x = saved[0], &w = saved[1];
+    const Incidence inc = load_incidence(ctx, "");
+    const Tensor g = go[0].contiguous(); // dtype of x, in which the forward ran
+    Tensor gx, gw;
+    if (need_x) gx = laplacian_apply(g, w, inc, "mesh_laplacian_backward"); // the operator is symmetric
+    if (need_w) {
+      const auto sizes = ctx->saved_data["w_sizes"].toIntVector();
+      const int64_t N = g.size(0), wB = sizes.size() == 3 ? sizes[0] : 1;
+      gw = out_empty({wB, inc.F, 3}, g.options());
+      check_status(drtk_amd_geometry_laplacian_grad_weights(
+                       dtype_of(g, "mesh_laplacian_backward"), g.data_ptr(), x.data_ptr(), g.size(2),
+                       inc.vi32.data_ptr<int32_t>(), vi_stride(inc), N, inc.V, inc.F, wB, gw.data_ptr(), current_stream(g)),
+                   "mesh_laplacian_backward");
+      gw = gw.view(sizes).to(static_cast<at::ScalarType>(ctx->saved_data["w_dtype"].toInt()));
+    }
+    return {gx, Tensor(), gw};
+  }
+};
+Tensor mesh_laplacian_autograd(const Tensor& x, const Tensor& vi, const c10::optional<Tensor>& weights) {
+  return MeshLaplacianFunction::apply(x, vi, weights)[0];
+}
+
+// ---------------------------------------------------------------------------------------------
 // incidence and cache (extension)
 // ---------------------------------------------------------------------------------------------
 std::tuple<Tensor, Tensor> vertex_incidence(const Tensor& vi, int64_t num_vertices) {
@@ -624,6 +777,12 @@ std::tuple<Tensor, Tensor> face_dpdt_cpu(const Tensor&, const Tensor&, const Ten
 Tensor vert_binormals_cpu(const Tensor&, const Tensor&, const Tensor&, const Tensor&) {
   no_cpu("vert_binormals");
 }
+Tensor cotangent_weights_cpu(const Tensor&, const Tensor&) {
+  no_cpu("cotangent_weights");
+}
+Tensor mesh_laplacian_cpu(const Tensor&, const Tensor&, const c10::optional<Tensor>&) {
+  no_cpu("mesh_laplacian");
+}
 
 } // namespace
 
@@ -633,6 +792,8 @@ TORCH_LIBRARY_FRAGMENT(drtk_amd_ext, m) {
   m.def("face_attribute_to_vert(Tensor v, Tensor vi, Tensor attr) -> Tensor");
   m.def("face_dpdt(Tensor v, Tensor vt, Tensor vi, Tensor vti) -> (Tensor, Tensor)");
   m.def("vert_binormals(Tensor v, Tensor vt, Tensor vi, Tensor vti) -> Tensor");
+  m.def("cotangent_weights(Tensor v, Tensor vi) -> Tensor");
+  m.def("mesh_laplacian(Tensor x, Tensor vi, Tensor? weights=None) -> Tensor");
   m.def("vertex_incidence(Tensor vi, int num_vertices) -> (Tensor, Tensor)", &vertex_incidence);
   m.def("geometry_cache_stats() -> int[]", &geometry_cache_stats);
   m.def("geometry_cache_clear() -> ()", &geometry_cache_clear);
@@ -643,6 +804,8 @@ TORCH_LIBRARY_IMPL(drtk_amd_ext, Autograd, m) {
   m.impl("face_attribute_to_vert", &face_attribute_to_vert_autograd);
   m.impl("face_dpdt", &face_dpdt_autograd);
   m.impl("vert_binormals", &vert_binormals_autograd);
+  m.impl("cotangent_weights", &cotangent_weights_autograd);
+  m.impl("mesh_laplacian", &mesh_laplacian_autograd);
 }
 TORCH_LIBRARY_IMPL(drtk_amd_ext, CUDA, m) {
   m.impl("face_info", &face_info_hip);
@@ -650,6 +813,8 @@ TORCH_LIBRARY_IMPL(drtk_amd_ext, CUDA, m) {
   m.impl("face_attribute_to_vert", &face_attribute_to_vert_hip);
   m.impl("face_dpdt", &face_dpdt_hip);
   m.impl("vert_binormals", &vert_binormals_hip);
+  m.impl("cotangent_weights", &cotangent_weights_hip);
+  m.impl("mesh_laplacian", &mesh_laplacian_hip);
 }
 TORCH_LIBRARY_IMPL(drtk_amd_ext, CPU, m) {
   m.impl("face_info", &face_info_cpu);
@@ -657,4 +822,6 @@ TORCH_LIBRARY_IMPL(drtk_amd_ext, CPU, m) {
   m.impl("face_attribute_to_vert", &face_attribute_to_vert_cpu);
   m.impl("face_dpdt", &face_dpdt_cpu);
   m.impl("vert_binormals", &vert_binormals_cpu);
+  m.impl("cotangent_weights", &cotangent_weights_cpu);
+  m.impl("mesh_laplacian", &mesh_laplacian_cpu);
 }

@@ -6,6 +6,9 @@ and a vertex pass that sums through the cached vertex incidence of the index ten
 chunk pass where a vertex is in more than 256 face corners -- bitwise reproducible (no float atomics).  Everything else -- CPU tensors, other dtypes -- takes the PyTorch formulation below.
 Index tensors may be int32 or int64.
 
+`cotangent_weights` and `mesh_laplacian` are this package's additions on the same passes: the mesh regulariser of a
+geometry fit (INTEGRATION.md "Mesh regularisers"), which the reference leaves to a padded table built on the host.
+
 Two differences from the reference on the HIP route:
 - face_dpdt (and vert_binormals) of a face whose UV matrix is singular gives the non-finite result of the closed-form
   2x2 inverse where the reference raises (a kernel cannot raise without synchronising); the PyTorch formulation raises
@@ -52,7 +55,7 @@ def _corners(x: th.Tensor, vi: th.Tensor) -> th.Tensor:
     """x [N,V,C], vi [F,3] / [B,F,3] -> the corner values [N,F,3,C]"""
     n, c = x.shape[0], x.shape[-1]
     t = _topology(vi, n)
-    flat = t.reshape(n, -1, 1).expand(-1, -1, c)
+    flat = t.reshape(n, 3 * t.shape[1], 1).expand(-1, -1, c)  # (sizes spelled out: n may be 0)
     return th.gather(x, 1, flat).view(n, t.shape[1], 3, c)
 
 
@@ -87,6 +90,32 @@ def _face_dpdt_torch(v, vt, vi, vti):
     dpdb = v012[:, :, 1:3] - v012[:, :, 0:1]
     dtdb = t012[:, :, 1:3] - t012[:, :, 0:1]
     return th.linalg.inv(dtdb) @ dpdb, v012
+
+
+def _cotangent_weights_torch(v, vi):
+    p = _corners(v, vi)  # [N,F,3,3]
+    with th.no_grad():
+        ok = th.linalg.vector_norm(th.linalg.cross(p[:, :, 0] - p[:, :, 2], p[:, :, 1] - p[:, :, 0], dim=-1), dim=-1) > 0
+    # a face whose |c| > 0 is false is computed from zeros, so that neither its values nor its gradients meet a NaN
+    p = th.where(ok[..., None, None], p, th.zeros_like(p))
+    c = th.linalg.cross(p[:, :, 0] - p[:, :, 2], p[:, :, 1] - p[:, :, 0], dim=-1)
+    two_nrm = 2 * th.where(ok, th.linalg.vector_norm(c, dim=-1), th.ones_like(ok, dtype=p.dtype))
+    dots = ((p.roll(-1, 2) - p) * (p.roll(-2, 2) - p)).sum(-1)  # [N,F,3]: (p_{k+1} - p_k) . (p_{k+2} - p_k)
+    return th.where(ok[..., None], dots / two_nrm[..., None], th.zeros_like(dots))
+
+
+def _mesh_laplacian_torch(x, vi, weights):
+    n, num_v, c = x.shape
+    t = _topology(vi, n)
+    xc = _corners(x, vi)  # [N,F,3,C]
+    if weights is None:
+        w = th.full((1, t.shape[1], 3), 0.5, dtype=x.dtype, device=x.device)
+    else:
+        w = weights if weights.dim() == 3 else weights[None]
+    # per (face, corner k) the row of vertex a_k: w[k+1] (x[a_{k+2}] - x[a_k]) + w[k+2] (x[a_{k+1}] - x[a_k])
+    rows = w.roll(-1, 2)[..., None] * (xc.roll(-2, 2) - xc) + w.roll(-2, 2)[..., None] * (xc.roll(-1, 2) - xc)
+    idx = t.reshape(n, 3 * t.shape[1], 1).expand(-1, -1, c)
+    return th.zeros(n, num_v, c, dtype=rows.dtype, device=x.device).scatter_add(1, idx, rows.reshape(n, 3 * t.shape[1], c))
 
 
 # --- public API ---------------------------------------------------------------------------------------------------
@@ -165,6 +194,32 @@ def vert_binormals(v: th.Tensor, vt: th.Tensor, vi: th.Tensor, vti: th.Tensor) -
         return _ops().vert_binormals(v, vt, vi, vti)
     dpdt_t, _ = _face_dpdt_torch(v, vt, vi, vti)
     return thf.normalize(_face_attribute_to_vert_torch(v, vi, dpdt_t[:, :, 0, :]), dim=-1)
+
+
+@th.compiler.disable
+def cotangent_weights(v: th.Tensor, vi: th.Tensor) -> th.Tensor:
+    """Cotangent weights [N,F,3] of the faces `vi` ([F,3], [1,F,3] or [N,F,3]) of `v` [N,V,3]: with corners
+    a0, a1, a2 = vi[f], w[n,f,k] = dot(p_{k+1} - p_k, p_{k+2} - p_k) / (2 |c|) = cot(angle at corner k) / 2, the weight
+    of the edge opposite corner k (a_{k+1} -- a_{k+2}); c = (p0 - p2) x (p1 - p0) as in face_info.  Where |c| > 0 is
+    false (duplicate or collinear corners, or a NaN) all three weights are exactly 0 and the face gives `v` no gradient.
+    Differentiable with respect to `v`.  This package's addition (the reference has no such function)."""
+    if _hip(v, idx=(vi,)):
+        return _ops().cotangent_weights(v, vi)
+    return _cotangent_weights_torch(v, vi)
+
+
+@th.compiler.disable
+def mesh_laplacian(x: th.Tensor, vi: th.Tensor, weights: Optional[th.Tensor] = None) -> th.Tensor:
+    """The weighted graph Laplacian [N,V,C] of `x` [N,V,C] over the faces `vi` ([F,3], [1,F,3] or [N,F,3]):
+    out[n,i] = sum_j w_ij (x[n,j] - x[n,i]) (negative semidefinite for non-negative weights), where the face weight
+    `weights[f,k]` ([F,3], [1,F,3] or [N,F,3], e.g. `cotangent_weights`) belongs to the edge opposite corner k and an
+    edge's w_ij is the sum over the faces that hold it.  `weights=None` is the uniform Laplacian: every face edge weighs
+    1/2, so an interior manifold edge totals 1 and a boundary edge 1/2.  An unreferenced vertex gives 0; a face that lists
+    a vertex twice adds a zero difference for that edge.  Differentiable with respect to `x` and `weights`.  This
+    package's addition (the reference has no such function)."""
+    if _hip(x, weights, idx=(vi,)):
+        return _ops().mesh_laplacian(x, vi, weights)
+    return _mesh_laplacian_torch(x, vi, weights)
 
 
 def index(x: th.Tensor, idxs: th.Tensor, dim: int) -> th.Tensor:

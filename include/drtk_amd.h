@@ -644,6 +644,48 @@ int drtk_amd_geometry_vertex_gather(
     int64_t num_chunks, int64_t B, int64_t N, int64_t V, int64_t F, int normalize, void* out, void* vert_sums,
     void* workspace, size_t workspace_bytes, drtk_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mesh regulariser -- cotangent weights and the weighted graph Laplacian of a triangle mesh (no counterpart in the
+ * reference's library; its hand-fitting tutorial builds a padded table on the host), on the passes and the vertex
+ * incidence of "Mesh geometry" above; shapes, strides and trust in the incidence as there.
+ *
+ * Face f has corners a0, a1, a2 = vi[f]; weight [f,k] belongs to the edge OPPOSITE corner k, a_{k+1} -- a_{k+2}
+ * (indices mod 3).
+ * cot_weights: weights [N,F,3], w[n,f,k] = dot(p_{k+1} - p_k, p_{k+2} - p_k) / (2 |c|) = cot(angle at corner k) / 2 with
+ *   c = (p0 - p2) x (p1 - p0); exactly 0 for all three k where |c| > 0 is false (c zero or NaN).
+ * cot_weights_backward: per-corner rows pos_rows [N,F,3,3] of grad_v from grad_weights [N,F,3] (zero rows for a face
+ *   with the degenerate zeros); reduce them with vertex_gather (per_corner = 1, A = 3).
+ * laplacian: out [N,V,C] from x [N,V,C] (contiguous, C >= 1):
+ *     out[n,i,:] = sum over the entries (f,k) of vertex i's incidence row, in entry order, of
+ *                  w[f,k+1] * (x[a_{k+2}] - x[i]) + w[f,k+2] * (x[a_{k+1}] - x[i])
+ *   = sum_j w_ij (x_j - x_i); each bracket is evaluated as written and then added; a chunked row adds its chunk sums in
+ *   chunk order.  weights [N,F,3] (w_sN = 3F) or one [F,3] for all views (w_sN = 0), independent of the topology's
+ *   batch; weights NULL (w_sN = 0): every w is 1/2 (the uniform Laplacian: an interior manifold edge totals 1) and no
+ *   weight is read.  vi / vi_sN must be the topology the incidence was built from: vi_sN = 0 with B = 1, 3F with
+ *   B = N.  The operator is symmetric: its backward with respect to x is the same call on the gradient.  With chunks
+ *   the call needs a workspace of _workspace_bytes.
+ * laplacian_grad_weights: grad_weights [weights_B,F,3], weights_B = N or 1,
+ *     [n,f,k] = -dot(grad_out[a_{k+1}] - grad_out[a_{k+2}], x[a_{k+1}] - x[a_{k+2}]) over the C channels, ascending;
+ *   weights_B = 1 (shared weights): the views' dots subtracted from 0 in ascending n.
+ * Results are bitwise reproducible: every sum has one fixed order, independent of the launch shape.
+ */
+int drtk_amd_geometry_cot_weights(
+    drtk_dtype_t dtype, const void* v, int64_t v_sN, const int32_t* vi, int64_t vi_sN, int64_t N, int64_t V, int64_t F,
+    void* weights, drtk_stream_t stream);
+int drtk_amd_geometry_cot_weights_backward(
+    drtk_dtype_t dtype, const void* v, int64_t v_sN, const int32_t* vi, int64_t vi_sN, int64_t N, int64_t V, int64_t F,
+    const void* grad_weights, void* pos_rows, drtk_stream_t stream);
+int drtk_amd_geometry_laplacian_workspace_bytes(
+    drtk_dtype_t dtype, int64_t N, int64_t B, int64_t num_chunks, int64_t C, size_t* bytes);
+int drtk_amd_geometry_laplacian(
+    drtk_dtype_t dtype, const void* x, int64_t C, const int32_t* vi, int64_t vi_sN, const void* weights, int64_t w_sN,
+    const int32_t* crow, const int32_t* entries, const int32_t* chunk_ptr, const int32_t* chunk_begin,
+    const int32_t* chunk_row, int64_t num_chunks, int64_t B, int64_t N, int64_t V, int64_t F, void* out, void* workspace,
+    size_t workspace_bytes, drtk_stream_t stream);
+int drtk_amd_geometry_laplacian_grad_weights(
+    drtk_dtype_t dtype, const void* grad_out, const void* x, int64_t C, const int32_t* vi, int64_t vi_sN, int64_t N,
+    int64_t V, int64_t F, int64_t weights_B, void* grad_weights, drtk_stream_t stream);
+
 /* Diagnostics: compares the rasterizer's reciprocal-based exact division with the IEEE `/` on `count`
  * pseudo-random operand pairs on the device; *d_mismatches (device memory) receives the number of
  * differing results (must be 0). */
