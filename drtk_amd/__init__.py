@@ -46,6 +46,7 @@ from drtk_amd.rasterize import (  # noqa: F401
 )
 from drtk_amd.render import render  # noqa: F401
 from drtk_amd.screen_space_uv_derivative import screen_space_uv_derivative  # noqa: F401
+from drtk_amd.shade import shade  # noqa: F401
 from drtk_amd.transform import transform, transform_with_v_cam  # noqa: F401
 
 __version__ = "0.1.0"
@@ -62,7 +63,9 @@ __version__ = "0.1.0"
 # alias-free up/down-sampling and low-pass filtering); the `drtk` drop-in package does not lift these three yet --
 # INTEGRATION.md.  `cotangent_weights` and `mesh_laplacian` (the mesh regulariser of a geometry fit: cotangent or uniform
 # Laplacian through the cached vertex incidence, one launch each way) are this package's additions too, and stay out of the
-# drop-in (the reference has no such names).  `transform` / `transform_with_v_cam` serve the pinhole camera and, on the HIP device, the reference's
+# drop-in (the reference has no such names).  `shade` (the per-pixel Blinn-Phong shading of a render-and-compare step --
+# Lambert, ambient, highlight, background select and gamma in one fused pass each way, the parameter gradients summed in a
+# fixed order) is an addition of the same kind and stays out of the drop-in as well.  `transform` / `transform_with_v_cam` serve the pinhole camera and, on the HIP device, the reference's
 # distortion models (radial-tangential, fisheye, fisheye62 with its lookup table, per-view lists) in one fused kernel each
 # way; the field-of-view estimators live in drtk_amd.transform (`estimate_rt_fov`, `estimate_fisheye_fov`,
 # `estimate_fisheye62_fov`) and in the drop-in's drtk.utils.  Not provided: the pure-PyTorch `*_ref` models (out of scope).
@@ -82,6 +85,7 @@ __all__ = [
     "mipmap_pyramid",
     "ssim",
     "photometric_loss",
+    "shade",
     "grid_scatter",
     "msi",
     "FilterType",

@@ -159,6 +159,9 @@ EXPORTS = [
     "drtk_amd_image_loss_workspace_bytes",
     "drtk_amd_image_loss_forward",
     "drtk_amd_image_loss_backward",
+    "drtk_amd_shade_workspace_bytes",
+    "drtk_amd_shade_forward",
+    "drtk_amd_shade_backward",
     "drtk_amd_filter2d_output_size",
     "drtk_amd_filter2d",
     "drtk_amd_screen_space_uv_derivative",
@@ -884,6 +887,95 @@ def image_loss_backward(img, target, weight, maps, grad_out, scalars, mode="ssim
         lib().drtk_amd_image_loss_backward(*head, _p(maps), _p(grad_out), _p(scalars), _p(grad), _stream(x, stream)),
         "image_loss_backward")
     return grad
+
+
+def shade_workspace_bytes(dtype, N, H, W) -> int:
+    out = ctypes.c_size_t(0)
+    dt = DRTK_F32 if dtype == th.float32 else DRTK_F64 if dtype == th.float64 else -1
+    _check(lib().drtk_amd_shade_workspace_bytes(ctypes.c_int(dt), _i(N), _i(H), _i(W), ctypes.byref(out)), "shade")
+    return out.value
+
+
+def _shade_args(normal_img, light_dir, albedo, ambient, index_img, pos_img, specular, shininess, background, gamma):
+    """(the tensors kept alive, the C arguments of the inputs, (N, C, H, W)) of the two shade entry points: images whose W
+    stride is 1 as they are with their strides {sN, sC, sH}, parameters contiguous with sN = 0 ([K]) or K ([N, K])."""
+    N, _, H, W = normal_img.shape
+    C = ambient.shape[-1]
+    keep, none3 = [], (ctypes.c_int64 * 3)(0, 0, 0)
+
+    def image(t, shape, dtype):
+        if t is None:
+            return _p(None), none3
+        assert tuple(t.shape) == tuple(shape) and t.dtype == dtype, (t.shape, shape, t.dtype)
+        t = t if (W <= 1 or t.stride(-1) == 1) else t.contiguous()
+        keep.append(t)
+        return _p(t), (ctypes.c_int64 * 3)(*(tuple(t.stride()[:-1]) + (0,))[:3])
+
+    def param(t, count):
+        if t is None:
+            return _p(None), _i(0)
+        assert t.dtype == normal_img.dtype and tuple(t.shape) in ((count,), (N, count)), (t.shape, count)
+        t = t.contiguous()
+        keep.append(t)
+        return _p(t), _i(count if t.ndim == 2 else 0)
+
+    dt = normal_img.dtype
+    albedo_img = albedo if albedo.ndim == 4 else None
+    args = (*image(normal_img, (N, 3, H, W), dt), *image(pos_img if specular is not None else None, (N, 3, H, W), dt),
+            *image(albedo_img, (N, C, H, W), dt), *image(background, (N, C, H, W), dt), *image(index_img, (N, H, W), th.int32),
+            *param(light_dir, 3), *param(None if albedo_img is not None else albedo, C), *param(ambient, C), *param(specular, C),
+            *param(shininess if specular is not None else None, 1), ctypes.c_double(0.0 if gamma is None else float(gamma)),
+            _i(N), _i(C), _i(H), _i(W))
+    return keep, args, (N, C, H, W)
+
+
+@_on_tensor_device
+def shade_forward(normal_img, light_dir, albedo, ambient, index_img=None, pos_img=None, specular=None, shininess=None,
+                  background=None, gamma=None, stream=None):
+    """out [N,C,H,W] of drtk_amd_shade_forward -- include/drtk_amd.h; the arguments of drtk_amd.shade."""
+    keep, args, (N, C, H, W) = _shade_args(normal_img, light_dir, albedo, ambient, index_img, pos_img, specular, shininess, background, gamma)
+    out = _out(N, C, H, W, dtype=normal_img.dtype, device=normal_img.device)
+    _check(lib().drtk_amd_shade_forward(ctypes.c_int(_dt(normal_img)), *args, _p(out), _stream(normal_img, stream)), "shade_forward")
+    return out
+
+
+SHADE_GRADS = ("normal_img", "pos_img", "albedo", "background", "light_dir", "ambient", "specular", "shininess")
+
+
+@_on_tensor_device
+def shade_backward(grad_out, normal_img, light_dir, albedo, ambient, index_img=None, pos_img=None, specular=None, shininess=None,
+                   background=None, gamma=None, want=SHADE_GRADS, stream=None):
+    """The gradients named in `want` (of SHADE_GRADS) as a dict, each in the shape of its argument -- a parameter given as
+    [K] receives the sum over the views; a name whose argument is absent (or pos_img / shininess without specular) is left
+    out.  drtk_amd_shade_backward -- include/drtk_amd.h."""
+    keep, args, (N, C, H, W) = _shade_args(normal_img, light_dir, albedo, ambient, index_img, pos_img, specular, shininess, background, gamma)
+    given = {"normal_img": normal_img, "pos_img": pos_img if specular is not None else None, "albedo": albedo, "background": background,
+             "light_dir": light_dir, "ambient": ambient, "specular": specular, "shininess": shininess if specular is not None else None}
+    grads = {k: _out(*given[k].shape, dtype=normal_img.dtype, device=normal_img.device) for k in SHADE_GRADS
+             if k in want and given[k] is not None}
+    grad_out = grad_out.to(normal_img.dtype).contiguous()
+    assert tuple(grad_out.shape) == (N, C, H, W), grad_out.shape
+    albedo_is_image = albedo.ndim == 4
+
+    def image(k, on=True):
+        return _p(grads.get(k) if on else None)
+
+    def param(k, count, on=True):
+        g = grads.get(k) if on else None
+        return _p(g), _i(count if g is not None and g.ndim == 2 else 0)
+
+    params = [k for k in ("light_dir", "ambient", "specular", "shininess") if k in grads] + (["albedo"] if "albedo" in grads and not albedo_is_image else [])
+    nbytes, ws = 0, None
+    if params:
+        nbytes = shade_workspace_bytes(normal_img.dtype, N, H, W)
+        ws = _out(nbytes, dtype=th.uint8, device=normal_img.device)
+    _check(
+        lib().drtk_amd_shade_backward(
+            ctypes.c_int(_dt(normal_img)), _p(grad_out), *args, image("normal_img"), image("pos_img"), image("albedo", albedo_is_image),
+            image("background"), *param("light_dir", 3), *param("albedo", C, not albedo_is_image), *param("ambient", C),
+            *param("specular", C), *param("shininess", 1), _p(ws), ctypes.c_size_t(nbytes), _stream(normal_img, stream)),
+        "shade_backward")
+    return grads
 
 
 def filter2d_output_size(size, k, up=1, down=1) -> int:

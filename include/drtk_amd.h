@@ -513,6 +513,49 @@ int drtk_amd_image_loss_backward(
     const void* scalars, void* grad_img, drtk_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * shade -- Blinn-Phong deferred shading of an interpolated G-buffer, one fused pass each way.  No reference counterpart (the
+ * reference's tutorial writes it in PyTorch).  Per pixel of view n, in the tensors' type, unit(x) = x / max(||x||, 1e-12):
+ *   L = unit(light_dir);  nv = unit(normal);  d = max(-(nv . L), 0);  col[c] = albedo[c] (d + ambient[c])
+ *   with specular != NULL:  w = unit(pos);  h = unit(L - w);  b = max(-(h . nv), 1e-8);  col[c] += b^shininess specular[c]
+ *   out[c] = col[c] where index_img is NULL or != -1, else background[c] (0 without one)
+ *   with gamma > 0:  out[c] = max(out[c], 0)^(1 / gamma), background pixels included.  gamma == 0: no such step.
+ *   normal_img, pos_img [N,3,H,W], albedo_img, background [N,C,H,W]: W stride 1, strides {sN, sC, sH} in elements, all >= 0
+ *     (channel slices, view slices, crops and a view-shared background with sN = 0 are read in place); index_img [N,H,W]
+ *     int32, strides {sN, sH}.  Element alignment is enough.  Exactly one of albedo (a vector) and albedo_img is given.
+ *   light_dir [3], albedo, ambient, specular [C], shininess [1]: one per view (`_sN` = the count) or shared (`_sN` = 0).
+ *     1 <= C <= 4.  specular != NULL requires pos_img and shininess.
+ *   out [N,C,H,W] contiguous, written fully.  Where index_img == -1 none of normal_img, pos_img, albedo_img is read; where
+ *   it is not, background is not.
+ * Backward: the derivative of the above; d passes a gradient only where -(nv . L) > 0, b only where -(h . nv) > 1e-8, the
+ *   gamma step only where its argument is > 0 (else exactly 0), unit(x) with ||x|| <= 1e-12 is a constant.  Every gradient
+ *   pointer may be NULL (not wanted, not computed); the image gradients are contiguous and written fully (0 at background
+ *   pixels for the foreground images, 0 at foreground pixels for grad_background); a parameter gradient is one per view
+ *   (`_sN` = the count) or the sum over the views (`_sN` = 0), written fully.  The parameter terms are accumulated in
+ *   double: one row of 16 doubles per workgroup in `workspace` (drtk_amd_shade_workspace_bytes, 16-byte aligned, looked at
+ *   only when a parameter gradient is wanted; alignment is judged before size), added in a fixed order by a second launch,
+ *   and by a third for gradients shared by N > 1 views.  No atomics, no zero-fill: bitwise reproducible.  Enqueues only.
+ * Judged first, before any pointer: dtype (DRTK_F32, DRTK_F64), N, H, W >= 0, H W < 2^31, 1 <= C <= 4, gamma >= 0 and
+ *   finite, the `_sN` values; then N == 0 or H W == 0 is DRTK_OK without a launch.
+ */
+int drtk_amd_shade_workspace_bytes(drtk_dtype_t dtype, int64_t N, int64_t H, int64_t W, size_t* bytes);
+int drtk_amd_shade_forward(
+    drtk_dtype_t dtype, const void* normal_img, const int64_t* normal_strides, const void* pos_img, const int64_t* pos_strides,
+    const void* albedo_img, const int64_t* albedo_img_strides, const void* background, const int64_t* background_strides,
+    const int32_t* index_img, const int64_t* index_strides, const void* light_dir, int64_t light_dir_sN, const void* albedo,
+    int64_t albedo_sN, const void* ambient, int64_t ambient_sN, const void* specular, int64_t specular_sN, const void* shininess,
+    int64_t shininess_sN, double gamma, int64_t N, int64_t C, int64_t H, int64_t W, void* out, drtk_stream_t stream);
+int drtk_amd_shade_backward(
+    drtk_dtype_t dtype, const void* grad_out, const void* normal_img, const int64_t* normal_strides, const void* pos_img,
+    const int64_t* pos_strides, const void* albedo_img, const int64_t* albedo_img_strides, const void* background,
+    const int64_t* background_strides, const int32_t* index_img, const int64_t* index_strides, const void* light_dir,
+    int64_t light_dir_sN, const void* albedo, int64_t albedo_sN, const void* ambient, int64_t ambient_sN, const void* specular,
+    int64_t specular_sN, const void* shininess, int64_t shininess_sN, double gamma, int64_t N, int64_t C, int64_t H, int64_t W,
+    void* grad_normal_img, void* grad_pos_img, void* grad_albedo_img, void* grad_background, void* grad_light_dir,
+    int64_t grad_light_dir_sN, void* grad_albedo, int64_t grad_albedo_sN, void* grad_ambient, int64_t grad_ambient_sN,
+    void* grad_specular, int64_t grad_specular_sN, void* grad_shininess, int64_t grad_shininess_sN, void* workspace,
+    size_t workspace_bytes, drtk_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * screen_space_uv_derivative -- vt_dxdy_img [N,H,W,2,2] = [[du/dx, dv/dx],[du/dy, dv/dy]] per pixel, the
  * Jacobian input of mipmap_grid_sampler_2d; replaces the PyTorch composite
  * drtk/screen_space_uv_derivative.py:15-80 (face_dpdt + 2x interpolate + project_points_grad + inv_ex +
