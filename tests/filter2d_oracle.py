@@ -251,7 +251,11 @@ def family_case(up, down, k):
 def family_expected(up, down, k, padding, half=False):
     """The oracle on a family's case, computed once: out / grad in float32 and float64 and the accumulated magnitudes of
     both, like `expected`; with `half` on the inputs rounded to float16 (what a float16 image holds)."""
-    x, f, gout = family_case(up, down, k)
+    return expected_on(*family_case(up, down, k), up, down, padding, half)
+
+
+def expected_on(x, f, gout, up, down, padding, half=False):
+    """family_expected on any float32 tensors x [N,C,H,W] (H and W multiples of `down`), f [k], grad_out."""
     if half:
         x, gout = x.half().float(), gout.half().float()
     reflect = padding == "reflection"

@@ -13,7 +13,8 @@ The first case shows that a damaged guard is reported.  The image losses run the
 257, 297 and 513 partial sums in the slot workspace, whose size drtk_amd_image_loss_workspace_bytes gave), both precisions
 and paddings, plain and weighted, forward with the gradient maps and backward; mipmap_pyramid the ragged shapes of its test
 module at full depth, every level and grad_input element-aligned at once, with all gradients and with one absent; then the
-first 20 seeds of tests/fuzz_image_ops.py.  Oracles, bounds and helpers are those of the operators' own test
+first 20 seeds of tests/fuzz_image_ops.py and the first 20 of tests/fuzz_added_ops.py (filter2d, composite_layers, shade,
+mesh_laplacian and msi on random shapes, layouts and options).  Oracles, bounds and helpers are those of the operators' own test
 modules, which this script imports.  Left out: what the torch operators allocate in C++ (only the binding has guards) and
 grad_grid of grid_scatter (allocated with the grid's strides, outside `_out`)."""
 import argparse
@@ -203,6 +204,16 @@ def fuzz_image_ops_case(seed):
         raise AssertionError(f"{F.describe(c)}: {e}") from e
 
 
+def fuzz_added_ops_case(seed):
+    import fuzz_added_ops as F
+
+    c = F.make_case(seed)
+    try:
+        F.run_case(c, check_guards=False)  # they are checked, and counted, after the case
+    except AssertionError as e:
+        raise AssertionError(f"{F.describe(c)}: {e}") from e
+
+
 def cases():
     """[(name, function, arguments)], in the order they run"""
     import image_loss_oracle
@@ -244,6 +255,8 @@ def cases():
             out.append((f"mipmap_pyramid/{'x'.join(map(str, shape))}/{TAG[dtype]}", mipmap_pyramid_case, (shape, dtype, (0, 1, 3, 7)[i])))
     for seed in range(20):
         out.append((f"fuzz_image_ops/seed{seed}", fuzz_image_ops_case, (seed,)))
+    for seed in range(20):
+        out.append((f"fuzz_added_ops/seed{seed}", fuzz_added_ops_case, (seed,)))
     assert len({c[0] for c in out}) == len(out)
     return out
 

@@ -159,19 +159,24 @@ def case(name):
     """(v [N,V,3], x [N,V,C], g [N,V,C] float64, vi int64 [F,3] or [N,F,3]); the views' vertices differ, and a per-view
     topology lists the same faces in another order and from another corner (degenerate faces stay last)"""
     mesh, n, c, per_view = CASES[name]
-    keep_last = 0
     if mesh == "one":
         v0, vi = th.tensor([[0.1, 0.0, 0.2], [1.0, 0.2, 0.0], [0.3, 0.9, 0.1]], dtype=th.float64), th.tensor([[0, 1, 2]])
     elif mesh == "soup":
         v0, vi = soup_mesh(257, 257, 3)
     elif mesh == "degenerate":
         v0, vi = with_degenerates(*grid_mesh(5, 7, 4))
-        keep_last = 2
     else:
         v0, vi = fan_mesh(int(mesh[3:]))
-    g = th.Generator().manual_seed(sum(map(ord, name)))
+    return build_case(v0, vi, n, c, per_view, sum(map(ord, name)), degenerate=mesh == "degenerate")
+
+
+def build_case(v0, vi, n, c, per_view, seed, degenerate=False):
+    """`case` for any mesh (v0 [V,3] float64, vi [F,3] int64), n views, c channels, drawn from a generator seeded with `seed`;
+    `degenerate`: the mesh went through with_degenerates (tests/fuzz_added_ops.py draws its own meshes)."""
+    keep_last = 2 if degenerate else 0
+    g = th.Generator().manual_seed(seed)
     v = v0[None] * (1 + 0.1 * th.arange(n, dtype=th.float64))[:, None, None] + 0.02 * th.randn(n, *v0.shape, dtype=th.float64, generator=g)
-    if mesh == "degenerate":
+    if degenerate:
         v[:, -3:] = v0[-3:]  # the collinear face keeps its integer coordinates
     x = th.randn(n, v0.shape[0], c, dtype=th.float64, generator=g)
     grad = th.randn(n, v0.shape[0], c, dtype=th.float64, generator=g)

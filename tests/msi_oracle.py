@@ -202,10 +202,20 @@ def forward_autograd(ray_o, ray_d, texture, sub_step_count, min_inv_r, max_inv_r
     return th.stack(outs)
 
 
-def make_case(seed, N, L, H, W, sigma_range, origin_radius, dtype=th.float32):
+def draw_rays(g, N, origin_radius):
+    """(origins uniform in a ball, unnormalised directions of length 0.1 ... 3) [N,3] float64 from the generator `g`"""
+    rnd = lambda *shape: th.rand(*shape, generator=g, dtype=th.float64)  # noqa: E731
+    unit = lambda x: x / x.norm(dim=1, keepdim=True)  # noqa: E731
+    o = unit(th.randn(N, 3, generator=g, dtype=th.float64)) * (rnd(N, 1) ** (1 / 3) * origin_radius)
+    d = unit(th.randn(N, 3, generator=g, dtype=th.float64)) * (rnd(N, 1) * 2.9 + 0.1)
+    return o, d
+
+
+def make_case(seed, N, L, H, W, sigma_range, origin_radius, dtype=th.float32, generator=None):
     """Seeded inputs: rgb in [-0.2, 1.2] (three texels in ten in [-0.2, 0), the others in [0, 1.2]), sigma uniform in sigma_range, origins
-    uniform in a ball, unnormalised directions of length 0.1 ... 3, grad_out in [-1, 1].  Generated in double and rounded to float32 (the rays always are float32)."""
-    g = th.Generator().manual_seed(seed)
+    uniform in a ball, unnormalised directions of length 0.1 ... 3, grad_out in [-1, 1].  Generated in double and rounded to float32 (the rays always are float32).
+    `generator`: one seeded by the caller, who goes on drawing from it (build_case), instead of a new one seeded with `seed`."""
+    g = th.Generator().manual_seed(seed) if generator is None else generator
     rnd = lambda *shape: th.rand(*shape, generator=g, dtype=th.float64)  # noqa: E731
     tex = th.empty(L, 4, H, W, dtype=th.float64)
     # three colour texels in ten negative: after sixteen taps of averaging a uniform draw hardly ever clamps.  With rgb uniform
@@ -214,9 +224,7 @@ def make_case(seed, N, L, H, W, sigma_range, origin_radius, dtype=th.float32):
     # cases must show, so the distribution inside the stated range was changed, not only the seed (now 16 - 35 %).
     tex[:, :3] = th.where(rnd(L, 3, H, W) < 0.3, rnd(L, 3, H, W) * -0.2, rnd(L, 3, H, W) * 1.2)
     tex[:, 3] = rnd(L, H, W) * (sigma_range[1] - sigma_range[0]) + sigma_range[0]
-    unit = lambda x: x / x.norm(dim=1, keepdim=True)  # noqa: E731
-    o = unit(th.randn(N, 3, generator=g, dtype=th.float64)) * (rnd(N, 1) ** (1 / 3) * origin_radius)
-    d = unit(th.randn(N, 3, generator=g, dtype=th.float64)) * (rnd(N, 1) * 2.9 + 0.1)
+    o, d = draw_rays(g, N, origin_radius)
     gout = rnd(N, 4) * 2 - 1
     return o.float(), d.float(), tex.float().to(dtype), gout.float().to(dtype)
 
@@ -237,13 +245,33 @@ def case(name):
     """(inputs, march arguments, fragile mask, float64 result, float32 result) of a case, computed once: the fragile rays'
     grad_out rows are zeroed, for the oracle here and for the kernel in the GPU suite alike."""
     if name not in _cache:
-        seed, N, (L, H, W), sub, mn, mx, stop, sig, rad = CASES[name]
-        o, d, tex, gout = make_case(seed, N, L, H, W, sig, rad)
-        args = (sub, mn, mx, stop)
-        fragile = march(o, d, tex.double(), *args).margin < FRAGILE_MARGIN
-        gout = gout.clone()
-        gout[fragile] = 0
-        r64 = march(o, d, tex.double(), *args, grad_out=gout.double())
-        r32 = march(o, d, tex, *args, grad_out=gout)
-        _cache[name] = ((o, d, tex, gout), args, fragile, r64, r32)
+        _cache[name] = build_case(*CASES[name])
     return _cache[name]
+
+
+REDRAW_ROUNDS = 20
+
+
+def build_case(seed, N, shape, sub, mn, mx, stop, sig, rad, redraw=False):
+    """`case` for any parameters (the tuple of a CASES entry).  `redraw` (tests/fuzz_added_ops.py, whose cases have too few
+    rays for a share of them to be left out): the fragile rays are drawn again from the same generator until none is left,
+    at most REDRAW_ROUNDS times, so that every ray is compared; the fragile mask returned is then empty."""
+    L, H, W = shape
+    g = th.Generator().manual_seed(seed)
+    o, d, tex, gout = make_case(seed, N, L, H, W, sig, rad, generator=g)
+    args = (sub, mn, mx, stop)
+    fragile = march(o, d, tex.double(), *args).margin < FRAGILE_MARGIN
+    if redraw:
+        for _ in range(REDRAW_ROUNDS):
+            if not bool(fragile.any()):
+                break
+            o2, d2 = draw_rays(g, int(fragile.sum()), rad)
+            o, d = o.clone(), d.clone()
+            o[fragile], d[fragile] = o2.float(), d2.float()
+            fragile = march(o, d, tex.double(), *args).margin < FRAGILE_MARGIN
+        assert not bool(fragile.any()), f"{int(fragile.sum())} fragile rays after {REDRAW_ROUNDS} redraws"
+    gout = gout.clone()
+    gout[fragile] = 0
+    r64 = march(o, d, tex.double(), *args, grad_out=gout.double())
+    r32 = march(o, d, tex, *args, grad_out=gout)
+    return ((o, d, tex, gout), args, fragile, r64, r32)

@@ -203,9 +203,14 @@ def case(name):
     both precisions see the same inputs): deterministic, and at a margin from every non-smooth point -- each pixel is drawn
     again until |n . L| >= 1e-3 and |h . n| >= 1e-3 (and ||L - w|| >= 0.1), input norms are >= 0.1, albedo, ambient, specular
     and background are >= 0.05 (so the value before gamma is >= 1e-3)."""
-    c = CASES[name]
+    return build_case(CASES[name], zlib.crc32(name.encode()), name)
+
+
+def build_case(c, seed, name="case"):
+    """`case` for any description `c` with the keys of a CASES entry (N, C, H, W, per_view, index, specular, background, gamma,
+    albedo_img), drawn from a generator seeded with `seed` (tests/fuzz_added_ops.py draws its own descriptions)."""
     N, C, H, W = c["N"], c["C"], c["H"], c["W"]
-    gen = th.Generator().manual_seed(zlib.crc32(name.encode()))
+    gen = th.Generator().manual_seed(seed)
     f32 = lambda t: t.float().double()  # noqa: E731
     rand = lambda *s: th.rand(*s, generator=gen, dtype=th.float64)  # noqa: E731
 

@@ -23,20 +23,24 @@ DEV = "cuda:0"
 
 def hip(name, padding, dtype, api):
     """(out, grad_x or None) of the kernels as CPU tensors.  api: `python` (resample_filter under autograd) | `capi`."""
+    x, f, gout, up, down = O.make_case(name)
+    return hip_on(x.to(DEV, dtype), f.to(DEV), gout.to(DEV, dtype), up, down, padding, api, O.divisible(name))
+
+
+def hip_on(x, f, gout, up, down, padding, api, divisible=True):
+    """`hip` on any device tensors, x in the layout it comes in (shared with tests/fuzz_added_ops.py)."""
     import drtk_amd
     from drtk_amd import capi
 
-    x, f, gout, up, down = O.make_case(name)
-    x, f, gout = x.to(DEV, dtype), f.to(DEV), gout.to(DEV, dtype)
     reflect = padding == "reflection"
     if api == "capi":
         out = capi.filter2d(x, f, up, down, reflect)
-        grad = capi.filter2d(gout, f, down, up, reflect, backward=True) if O.divisible(name) else None
+        grad = capi.filter2d(gout, f, down, up, reflect, backward=True) if divisible else None
     else:
-        x.requires_grad_(True), f.requires_grad_(True)
+        x, f = x.detach().requires_grad_(True), f.detach().requires_grad_(True)
         out = drtk_amd.resample_filter(x, f, up, down, padding)
         grad = None
-        if O.divisible(name):
+        if divisible:
             out.backward(gout)
             assert f.grad is None  # the filter gets no gradient
             grad = x.grad
@@ -146,11 +150,17 @@ def check_family(up, down, k, dtype, padding):
     oracle under the bounds of this file's docstring -- the oracle runs on what the image type holds (the inputs rounded to
     float16 for a half image) --, and, where (up, down, k) is a tuned family, the tuned instantiation against the generic
     one.  Shared with tests/guarded_added_ops.py.  -> {"out" | "grad_x": (worst error, its bound)} against the oracle."""
+    x, f, gout = O.family_case(up, down, k)
+    return check_inputs(x, f, gout, up, down, dtype, padding, O.family_expected(up, down, k, padding, dtype == th.float16))
+
+
+def check_inputs(x, f, gout, up, down, dtype, padding, e):
+    """check_family on any float32 CPU tensors x, f, grad_out with `e` the oracle's results on them, in the form of
+    O.family_expected (shared with tests/fuzz_added_ops.py)."""
     from drtk_amd import capi
 
-    x, f, gout = O.family_case(up, down, k)
+    k = f.shape[0]
     half = dtype == th.float16
-    e = O.family_expected(up, down, k, padding, half)
     reflect = padding == "reflection"
     fd = f.to(DEV)
     figures = {}

@@ -46,12 +46,27 @@ def hip_pipeline(v, x, grad, vi, api="ops"):
 def check_case(name, dtype, api="ops"):
     """float64: 1e-12 of each result's scale from the oracle; float32: within the project's float64-distance bound,
     max(1e-5 max|f64|, 3 |oracle_f32 - f64|), the oracles on the float32 inputs."""
-    v, x, grad, vi = O.case(name)
+    return check_inputs(*O.case(name), dtype, api, name, degenerate=name.startswith("degenerate"))
+
+
+def check_inputs(v, x, grad, vi, dtype, api, name, degenerate=False):
+    """check_case on any inputs of O.case / O.build_case (shared with tests/fuzz_added_ops.py)."""
     v, x, grad = v.to(dtype), x.to(dtype), grad.to(dtype)
     got = hip_pipeline(v, x, grad, vi, api)
     r64 = O.reference(v, x, grad, vi, th.float64)
     r32 = O.reference(v, x, grad, vi, th.float32) if dtype == th.float32 else None
-    for k in KEYS:
+    compare(got, r64, r32, dtype, name)
+    if degenerate:
+        n = v.shape[0]
+        assert th.equal(got["weights"][:, -2:], th.zeros(n, 2, 3, dtype=dtype))  # duplicate-corner and collinear face
+        assert th.equal(got["grad_v"][:, -3:], th.zeros(n, 3, 3, dtype=dtype))   # which give v no gradient
+        assert th.equal(got["out"][:, -4], th.zeros(n, x.shape[2], dtype=dtype))  # the unreferenced vertex
+    return got
+
+
+def compare(got, r64, r32, dtype, name):
+    """Every result the float64 oracle `r64` has, under the two bounds of check_case (`r32`: the float32 oracle, or None)."""
+    for k in r64:
         assert got[k].dtype == dtype and got[k].shape == r64[k].shape, (name, k)
         assert float(r64[k].abs().max()) > 0, (name, k)
         err = float((got[k].double() - r64[k]).abs().max())
@@ -60,12 +75,6 @@ def check_case(name, dtype, api="ops"):
             assert err <= 1e-12 * float(r64[k].abs().max()), (name, k, err)
         else:
             assert_within_f64_distance(got[k], r32[k], r64[k], f"{name} {k}")
-    if name.startswith("degenerate"):
-        n = v.shape[0]
-        assert th.equal(got["weights"][:, -2:], th.zeros(n, 2, 3, dtype=dtype))  # duplicate-corner and collinear face
-        assert th.equal(got["grad_v"][:, -3:], th.zeros(n, 3, 3, dtype=dtype))   # which give v no gradient
-        assert th.equal(got["out"][:, -4], th.zeros(n, x.shape[2], dtype=dtype))  # the unreferenced vertex
-    return got
 
 
 @pytest.mark.parametrize("dtype", [th.float32, th.float64])

@@ -1424,7 +1424,8 @@ def test_added_operators_write_nothing_outside_their_outputs(guard):
     """The same for the operators the fuzzers above do not call -- filter2d, composite_layers, grid_scatter, msi,
     transform_distort, the geometry entry points, rasterize_layers, the image losses (their slot workspace, gradient maps
     and scalars) and mipmap_pyramid (every level element-aligned at once): tests/guarded_added_ops.py, a fixed list of
-    small cases with ragged ends against their oracles and the first 20 seeds of tests/fuzz_image_ops.py, sentinels intact
+    small cases with ragged ends against their oracles and the first 20 seeds of tests/fuzz_image_ops.py and of
+    tests/fuzz_added_ops.py, sentinels intact
     after every case, in a process of its own (the binding reads DRTK_CAPI_GUARD when it is imported).  Its first case shows
     that a damaged sentinel is reported."""
     import re
