@@ -47,6 +47,7 @@ from drtk_amd.rasterize import (  # noqa: F401
 from drtk_amd.render import render  # noqa: F401
 from drtk_amd.screen_space_uv_derivative import screen_space_uv_derivative  # noqa: F401
 from drtk_amd.shade import shade  # noqa: F401
+from drtk_amd.skin import skin, sparse_skin_weights  # noqa: F401
 from drtk_amd.transform import transform, transform_with_v_cam  # noqa: F401
 
 __version__ = "0.1.0"
@@ -65,7 +66,9 @@ __version__ = "0.1.0"
 # Laplacian through the cached vertex incidence, one launch each way) are this package's additions too, and stay out of the
 # drop-in (the reference has no such names).  `shade` (the per-pixel Blinn-Phong shading of a render-and-compare step --
 # Lambert, ambient, highlight, background select and gamma in one fused pass each way, the parameter gradients summed in a
-# fixed order) is an addition of the same kind and stays out of the drop-in as well.  `transform` / `transform_with_v_cam` serve the pinhole camera and, on the HIP device, the reference's
+# fixed order) is an addition of the same kind and stays out of the drop-in as well.  `skin` (linear blend skinning, the
+# step from rig parameters to geometry: forward and the gradients to the rest pose, the weights and the joint transforms,
+# no float atomics) with its companion `sparse_skin_weights` is one more, and stays out of the drop-in too.  `transform` / `transform_with_v_cam` serve the pinhole camera and, on the HIP device, the reference's
 # distortion models (radial-tangential, fisheye, fisheye62 with its lookup table, per-view lists) in one fused kernel each
 # way; the field-of-view estimators live in drtk_amd.transform (`estimate_rt_fov`, `estimate_fisheye_fov`,
 # `estimate_fisheye62_fov`) and in the drop-in's drtk.utils.  Not provided: the pure-PyTorch `*_ref` models (out of scope).
@@ -109,4 +112,6 @@ __all__ = [
     "vert_binormals",
     "cotangent_weights",
     "mesh_laplacian",
+    "skin",
+    "sparse_skin_weights",
 ]

@@ -179,6 +179,9 @@ EXPORTS = [
     "drtk_amd_geometry_laplacian_workspace_bytes",
     "drtk_amd_geometry_laplacian",
     "drtk_amd_geometry_laplacian_grad_weights",
+    "drtk_amd_skin_forward",
+    "drtk_amd_skin_backward_workspace_bytes",
+    "drtk_amd_skin_backward",
     "drtk_amd_selftest_exact_div",
     "drtk_amd_kernel_timing_begin",
     "drtk_amd_kernel_timing_report",
@@ -1283,6 +1286,103 @@ def geometry_laplacian_grad_weights(grad_out, x, vi, shared_weights=False, strea
                                                           _i(N), _i(V), _i(F), _i(wB), _p(gw), _stream(x, stream)),
            "geometry_laplacian_grad_weights")
     return gw
+
+
+SKIN_CHUNK = 512  # DRTK_SKIN_CHUNK of include/drtk_amd.h
+SKIN_MAX_SLOTS = 8  # DRTK_SKIN_MAX_SLOTS
+
+
+def joint_incidence_numpy(joint_idx, num_joints: int, chunk: int = SKIN_CHUNK):
+    """The joint incidence drtk_amd_skin_backward takes (include/drtk_amd.h, "Linear blend skinning"), built with numpy from
+    joint_idx [V,K] (-1: empty slot): (crow [J+1], entries, chunk_ptr [J+1], chunk_begin [C], chunk_joint [C]), int32.
+    Every row is cut into chunks of `chunk` entries."""
+    import numpy as np
+
+    t = np.asarray(joint_idx, dtype=np.int64).reshape(-1)
+    J = int(num_joints)
+    if t.size and (t.min() < -1 or t.max() >= J):
+        raise ValueError(f"joint_idx contains a joint index outside [-1, {J})")
+    keys = np.where(t < 0, J, t)
+    perm = np.argsort(keys, kind="stable")
+    crow = np.searchsorted(keys[perm], np.arange(J + 1), side="left").astype(np.int64)
+    nch = (np.diff(crow) + chunk - 1) // chunk
+    chunk_ptr = np.concatenate([[0], np.cumsum(nch)]).astype(np.int64)
+    chunk_joint = np.repeat(np.arange(J), nch)
+    chunk_begin = crow[chunk_joint] + (np.arange(len(chunk_joint)) - chunk_ptr[chunk_joint]) * chunk
+    return tuple(a.astype(np.int32) for a in (crow, perm, chunk_ptr, chunk_begin, chunk_joint))
+
+
+def _skin_args(v, joint_idx, joint_weights, transforms):
+    """-> (v contiguous, v_sN, idx, w, transforms read in place or copied, t_sN, t_sJ, N, V, J, K)"""
+    assert joint_idx.dtype == th.int32 and joint_idx.dim() == 2
+    assert transforms.dim() == 4 and transforms.shape[2] in (3, 4) and transforms.shape[3] == 4
+    assert joint_weights.shape == joint_idx.shape and joint_weights.dtype == v.dtype == transforms.dtype
+    N, J = transforms.shape[0], transforms.shape[1]
+    v = (v[None] if v.dim() == 2 else v).contiguous()
+    V, K = joint_idx.shape
+    assert v.shape[1:] == (V, 3) and v.shape[0] in (1, N)
+    t = transforms
+    s = t.stride()
+    if not (s[3] == 1 and s[2] == 4 and (J <= 1 or s[1] >= 12) and (N <= 1 or s[0] == 0 or s[0] >= (J - 1) * (s[1] if J > 1 else 0) + 12)):
+        t = t.contiguous()
+    t_sJ = t.stride(1) if J > 1 else 12
+    t_sN = t.stride(0) if N > 1 else 0
+    return v, (0 if v.shape[0] == 1 else 3 * V), joint_idx.contiguous(), joint_weights.contiguous(), t, t_sN, t_sJ, N, V, J, K
+
+
+@_on_tensor_device
+def skin_forward(v, joint_idx, joint_weights, transforms, stream=None):
+    """out [N,V,3] of v [N,V,3] / [1,V,3] / [V,3], int32 joint_idx [V,K] (entries in [-1, J), NOT checked here),
+    joint_weights [V,K] and transforms [N,J,3,4] / [N,J,4,4] (a [..., :3, :] view is read in place)."""
+    v, v_sN, idx, w, t, t_sN, t_sJ, N, V, J, K = _skin_args(v, joint_idx, joint_weights, transforms)
+    out = _out(N, V, 3, dtype=v.dtype, device=v.device)
+    _check(lib().drtk_amd_skin_forward(ctypes.c_int(_dt(v)), _p(v), _i(v_sN), _p(idx), _p(w), _p(t), _i(t_sN), _i(t_sJ),
+                                       _i(N), _i(V), _i(J), _i(K), _p(out), _stream(v, stream)), "skin_forward")
+    return out
+
+
+def skin_backward_workspace_bytes(dtype, N, num_chunks) -> int:
+    out = ctypes.c_size_t(0)
+    code = DRTK_F32 if dtype == th.float32 else DRTK_F64
+    _check(lib().drtk_amd_skin_backward_workspace_bytes(ctypes.c_int(code), _i(N), _i(num_chunks), ctypes.byref(out)),
+           "skin_backward")
+    return out.value
+
+
+@_on_tensor_device
+def skin_backward(grad_out, v, joint_idx, joint_weights, transforms, incidence=None, grads=("v", "weights", "transforms"),
+                  sum_views=None, stream=None):
+    """(grad_v, grad_weights, grad_transforms) of skin_forward, None for what `grads` does not name.  `incidence` =
+    joint_incidence_numpy(joint_idx, J) (device tensors, or numpy arrays copied here), needed for "transforms".
+    grad_v is [1,V,3] (the views' rows added, n ascending) where v was given as one row, else [N,V,3]; `sum_views`
+    overrides that.  grad_transforms has the shape of `transforms`."""
+    v, v_sN, idx, w, t, t_sN, t_sJ, N, V, J, K = _skin_args(v, joint_idx, joint_weights, transforms)
+    g = grad_out.contiguous()
+    assert g.shape == (N, V, 3) and g.dtype == v.dtype
+    if sum_views is None:
+        sum_views = v.shape[0] == 1
+    gv_B = 1 if sum_views else N
+    gv = _out(gv_B, V, 3, dtype=v.dtype, device=v.device) if "v" in grads else None
+    gw = _out(V, K, dtype=v.dtype, device=v.device) if "weights" in grads else None
+    gt = ws = None
+    rows = transforms.shape[2]
+    inc = [None] * 5
+    nch = need = 0
+    if "transforms" in grads:
+        inc = [th.as_tensor(a, dtype=th.int32, device=v.device).contiguous() for a in incidence]
+        assert inc[0].numel() == J + 1 and inc[2].numel() == J + 1
+        nch = inc[4].numel()
+        gt = _out(N, J, rows, 4, dtype=v.dtype, device=v.device)
+        need = skin_backward_workspace_bytes(v.dtype, N, nch)
+        ws = _out(max(need, 1), dtype=th.uint8, device=v.device)
+        assert ws.data_ptr() % 8 == 0
+    _check(
+        lib().drtk_amd_skin_backward(
+            ctypes.c_int(_dt(v)), _p(g), _p(v), _i(v_sN), _p(idx), _p(w), _p(t), _i(t_sN), _i(t_sJ), *(_p(a) for a in inc),
+            _i(nch), _i(N), _i(V), _i(J), _i(K), _i(gv_B), _p(gv), _p(gw), _i(rows), _p(gt), _p(ws), ctypes.c_size_t(need),
+            _stream(v, stream)),
+        "skin_backward")
+    return gv, gw, gt
 
 
 def edge_grad_backward_workspace_bytes(dtype, N, H, W) -> int:

@@ -729,6 +729,56 @@ int drtk_amd_geometry_laplacian_grad_weights(
     drtk_dtype_t dtype, const void* grad_out, const void* x, int64_t C, const int32_t* vi, int64_t vi_sN, int64_t N,
     int64_t V, int64_t F, int64_t weights_B, void* grad_weights, drtk_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Linear blend skinning (no counterpart in the reference's library): the posed vertices
+ *     out[n,i] = sum over the slots k ascending with joint_idx[i,k] >= 0 of w[i,k] * (R[n,j] v[n,i] + t[n,j]),  j = joint_idx[i,k]
+ * and the three gradients, without float atomics.
+ *
+ * Shapes: v [N,V,3] (v_sN = 3V, or 0: one [V,3] shared by the views); joint_idx int32 [V,K], 1 <= K <=
+ * DRTK_SKIN_MAX_SLOTS, entries in [-1, J): -1 is an empty slot (nothing added, its weight is not read, gradient 0);
+ * joint_weights [V,K], used as given; transforms: rows 0..2 of joint j of view n are the 12 consecutive elements at
+ * n*t_sN + j*t_sJ ([N,J,3,4]: t_sJ = 12; [N,J,4,4], whose fourth row is not read: t_sJ = 16; t_sN = J*t_sJ, more for a
+ * view of a larger tensor, or 0: one set for all views); out [N,V,3].  The kernels trust joint_idx (it is not validated
+ * on the device).
+ *
+ * Evaluation order (every product and sum as written, no contraction): M = 0; M += w[i,k] * T[n,j] over the slots in
+ * ascending k (the 3x4 is blended first); out_a = M[a][0]*x + M[a][1]*y + M[a][2]*z + M[a][3].  A vertex whose slots
+ * are all empty gives exactly 0.
+ *
+ * skin_backward: grad_out [N,V,3]; NULL outputs are skipped, at least one must be given.
+ *   grad_v [grad_v_B,V,3], grad_v_B = N or 1: M^T grad_out[n,i] (M's 3x3 part, blended as in the forward);
+ *     grad_v_B = 1: the views' rows added in ascending n.
+ *   grad_weights [V,K]: sum over n ascending of dot(grad_out[n,i], R[n,j] v[n,i] + t[n,j]); 0 for an empty slot.
+ *   grad_transforms [N,J,grad_t_rows,4], grad_t_rows = 3 or 4 (the fourth row receives exactly 0):
+ *     [n,j,a,b] = sum over the entries (i,k) with joint_idx[i,k] = j of w[i,k] * grad_out[n,i,a] * [v[n,i]; 1]_b,
+ *     accumulated in double for either dtype and rounded once.  It needs the JOINT INCIDENCE of joint_idx, built by the
+ *     caller once per index tensor (drtk_amd_ext::joint_incidence builds and caches it; drtk_amd/capi.py has a numpy
+ *     builder), and a workspace of _workspace_bytes (8-byte aligned):
+ *       crow        int32 [J+1]   joint j's entries are entries[crow[j] .. crow[j+1]-1]
+ *       entries     int32 [>= crow[J]]  the slots i*K+k that name the joint, ASCENDING within the joint
+ *       chunk_ptr   int32 [J+1]   joint j's chunks are chunk_ptr[j] .. chunk_ptr[j+1]-1; EVERY row is cut into
+ *                                 ceil(length / DRTK_SKIN_CHUNK) chunks (none for a joint nobody names, which gets 0)
+ *       chunk_begin int32 [C]     first entry of the chunk (crow[j] + c*DRTK_SKIN_CHUNK for the joint's c-th chunk)
+ *       chunk_joint int32 [C]     its joint
+ *     Order of the sum: within a chunk, lane l of a 64-lane wave adds the chunk's entries l, l+64, ... in that order,
+ *     the 64 lane sums are added in a butterfly (partner lane xor 32, 16, 8, 4, 2, 1), and a joint's chunk sums are added
+ *     in chunk order.
+ * Results are bitwise reproducible: every sum has one fixed order, independent of the launch shape.
+ */
+#define DRTK_SKIN_MAX_SLOTS 8
+#define DRTK_SKIN_CHUNK 512
+int drtk_amd_skin_forward(
+    drtk_dtype_t dtype, const void* v, int64_t v_sN, const int32_t* joint_idx, const void* joint_weights,
+    const void* transforms, int64_t t_sN, int64_t t_sJ, int64_t N, int64_t V, int64_t J, int64_t K, void* out,
+    drtk_stream_t stream);
+int drtk_amd_skin_backward_workspace_bytes(drtk_dtype_t dtype, int64_t N, int64_t num_chunks, size_t* bytes);
+int drtk_amd_skin_backward(
+    drtk_dtype_t dtype, const void* grad_out, const void* v, int64_t v_sN, const int32_t* joint_idx,
+    const void* joint_weights, const void* transforms, int64_t t_sN, int64_t t_sJ, const int32_t* crow,
+    const int32_t* entries, const int32_t* chunk_ptr, const int32_t* chunk_begin, const int32_t* chunk_joint,
+    int64_t num_chunks, int64_t N, int64_t V, int64_t J, int64_t K, int64_t grad_v_B, void* grad_v, void* grad_weights,
+    int64_t grad_t_rows, void* grad_transforms, void* workspace, size_t workspace_bytes, drtk_stream_t stream);
+
 /* Diagnostics: compares the rasterizer's reciprocal-based exact division with the IEEE `/` on `count`
  * pseudo-random operand pairs on the device; *d_mismatches (device memory) receives the number of
  * differing results (must be 0). */
