@@ -71,22 +71,27 @@ __device__ __forceinline__ void load_uv_corners(const T* __restrict__ vt, const 
   }
 }
 
-// dpdt_t = inv([t1-t0; t2-t0]) @ [p1-p0; p2-p0], the inverse in closed form (a singular UV matrix gives inf / nan)
-template <typename T>
+// dpdt_t = inv([t1-t0; t2-t0]) @ [p1-p0; p2-p0], the inverse in closed form (a singular UV matrix gives inf / nan).
+// In double whatever T is (a few operations per face): det = a0 b1 - a1 b0 cancels on a sliver UV triangle, and carried in
+// float such a face -- the largest entries of the output, and of the gradients through M^T gM M^T -- lost its condition
+// number times 2^-24, several times what a pivoted float inverse of the same matrix loses (tests/fuzz_geometry.py, seeds
+// 13, 99, 155 and 207).  The edge differences of float corners are exact in double, so a float result is the correctly
+// rounded one up to the last products.
 struct Dpdt {
-  T m[2][2]; // inv(dtdb_t)
-  T P[2][3]; // dpdb_t
+  double m[2][2]; // inv(dtdb_t)
+  double P[2][3]; // dpdb_t
 };
 template <typename T>
-__device__ __forceinline__ Dpdt<T> dpdt_setup(const T p[3][3], const T t[3][2]) {
-  Dpdt<T> r;
-  const T a0 = t[1][0] - t[0][0], a1 = t[1][1] - t[0][1];
-  const T b0 = t[2][0] - t[0][0], b1 = t[2][1] - t[0][1];
-  const T det = a0 * b1 - a1 * b0;
+__device__ __forceinline__ Dpdt dpdt_setup(const T p[3][3], const T t[3][2]) {
+  Dpdt r;
+  const double a0 = double(t[1][0]) - double(t[0][0]), a1 = double(t[1][1]) - double(t[0][1]);
+  const double b0 = double(t[2][0]) - double(t[0][0]), b1 = double(t[2][1]) - double(t[0][1]);
+  const double det = a0 * b1 - a1 * b0;
   r.m[0][0] = b1 / det, r.m[0][1] = -a1 / det;
   r.m[1][0] = -b0 / det, r.m[1][1] = a0 / det;
 #pragma unroll
-  for (int j = 0; j < 3; ++j) r.P[0][j] = p[1][j] - p[0][j], r.P[1][j] = p[2][j] - p[0][j];
+  for (int j = 0; j < 3; ++j)
+    r.P[0][j] = double(p[1][j]) - double(p[0][j]), r.P[1][j] = double(p[2][j]) - double(p[0][j]);
   return r;
 }
 
@@ -130,12 +135,12 @@ __global__ __launch_bounds__(kBlock) void geom_face_forward_kernel(
   if (dpdt || dpdt_u) {
     T t[3][2];
     load_uv_corners(vt + n * vt_sN, vti + f * 3, t);
-    const Dpdt<T> q = dpdt_setup(p, t);
+    const Dpdt q = dpdt_setup(p, t);
 #pragma unroll
     for (int r = 0; r < 2; ++r)
 #pragma unroll
       for (int j = 0; j < 3; ++j) {
-        const T x = q.m[r][0] * q.P[0][j] + q.m[r][1] * q.P[1][j];
+        const T x = T(q.m[r][0] * q.P[0][j] + q.m[r][1] * q.P[1][j]);
         if (dpdt) dpdt[i * 6 + r * 3 + j] = x;
         if (dpdt_u && r == 0) dpdt_u[i * 3 + j] = x;
       }
@@ -219,14 +224,14 @@ __global__ __launch_bounds__(kBlock) void geom_face_backward_kernel(
   } else {
     T t[3][2];
     load_uv_corners(vt + n * vt_sN, vti + f * 3, t);
-    const Dpdt<T> q = dpdt_setup(p, t);
-    T gD[2][3];
+    const Dpdt q = dpdt_setup(p, t);
+    double gD[2][3];
 #pragma unroll
     for (int r = 0; r < 2; ++r)
 #pragma unroll
-      for (int j = 0; j < 3; ++j) gD[r][j] = (g_dpdt ? g_dpdt[i * 6 + r * 3 + j] : T(0)) + (r == 0 ? gv[j] : T(0));
-    // D = M P:  gM = gD P^T, gP = M^T gD;  M = inv(A):  gA = -M^T gM M^T
-    T gM[2][2], gA[2][2], gP[2][3];
+      for (int j = 0; j < 3; ++j) gD[r][j] = double((g_dpdt ? g_dpdt[i * 6 + r * 3 + j] : T(0)) + (r == 0 ? gv[j] : T(0)));
+    // D = M P:  gM = gD P^T, gP = M^T gD;  M = inv(A):  gA = -M^T gM M^T  (in double, as M is)
+    double gM[2][2], gA[2][2], gP[2][3];
 #pragma unroll
     for (int r = 0; r < 2; ++r)
 #pragma unroll
@@ -240,22 +245,22 @@ __global__ __launch_bounds__(kBlock) void geom_face_backward_kernel(
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         // (M^T gM M^T)[r][s] = sum_kl M[k][r] gM[k][l] M[s][l]
-        const T x0 = q.m[0][r] * gM[0][0] + q.m[1][r] * gM[1][0];
-        const T x1 = q.m[0][r] * gM[0][1] + q.m[1][r] * gM[1][1];
+        const double x0 = q.m[0][r] * gM[0][0] + q.m[1][r] * gM[1][0];
+        const double x1 = q.m[0][r] * gM[0][1] + q.m[1][r] * gM[1][1];
         gA[r][s] = -(x0 * q.m[s][0] + x1 * q.m[s][1]);
       }
     T* uv = uv_rows + i * 6;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      uv[j] = -(gA[0][j] + gA[1][j]);
-      uv[2 + j] = gA[0][j];
-      uv[4 + j] = gA[1][j];
+      uv[j] = T(-(gA[0][j] + gA[1][j]));
+      uv[2 + j] = T(gA[0][j]);
+      uv[4 + j] = T(gA[1][j]);
     }
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
-      gp[0][j] = -(gP[0][j] + gP[1][j]);
-      gp[1][j] = gP[0][j];
-      gp[2][j] = gP[1][j];
+      gp[0][j] = T(-(gP[0][j] + gP[1][j]));
+      gp[1][j] = T(gP[0][j]);
+      gp[2][j] = T(gP[1][j]);
     }
     if (g_v012) {
 #pragma unroll

@@ -649,8 +649,8 @@ int drtk_amd_transform_distort_backward(
  *
  * face_forward: per (view, face) with c = (p0 - p2) x (p1 - p0): normals [N,F,3] = c / max(|c|, 1e-8),
  *   areas [N,F,1] = |c| / 2, edges [N,F,3,3] = (p1-p0, p0-p2, p2-p1), and with vt/vti: dpdt [N,F,2,3] =
- *   inv([t1-t0; t2-t0]) [p1-p0; p2-p0] (closed-form 2x2 inverse: a singular UV matrix gives inf / nan where the
- *   reference raises), dpdt_u [N,F,3] = its first row, v012 [N,F,3,3] = (p0, p1, p2).  NULL outputs are skipped;
+ *   inv([t1-t0; t2-t0]) [p1-p0; p2-p0] (closed-form 2x2 inverse, formed in double for either dtype, as are the
+ *   gradients through it: a singular UV matrix gives inf / nan where the reference raises), dpdt_u [N,F,3] = its first row, v012 [N,F,3,3] = (p0, p1, p2).  NULL outputs are skipped;
  *   at least one must be given.
  * face_backward: per-corner gradient rows pos_rows [N,F,3,3] (and, with vt given, uv_rows [N,F,3,2]) of the face
  *   pass from the optional upstream gradients grad_normals / grad_areas / grad_edges (vt NULL) or grad_dpdt /

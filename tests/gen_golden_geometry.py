@@ -4,14 +4,19 @@ drtk.utils.geometry (drtk/utils/geometry.py, pure PyTorch), imported from where 
 oracle/gen_golden_refpy.import_reference() (build machine only).  A process of its own: nothing of drtk_amd is
 imported.  Single torch thread => deterministic accumulation order.  No test imports this file.
 
-    python tests/gen_golden_geometry.py      # rewrites tests/golden/refpy_geometry_{f32,f64}.npz
+    python tests/gen_golden_geometry.py              # rewrites tests/golden/refpy_geometry_{f32,f64}.npz and the seam archives
+    python tests/gen_golden_geometry.py --seam-only  # rewrites tests/golden/refpy_geometry_seam_{f32,f64}.npz alone
 
 Meshes (prefix in the archive):
   band_   a UV sphere band (no pole rows): no degenerate face, 2 views, vi [F,3]; face_dpdt / vert_binormals too
   poles_  a UV sphere with its pole rows: zero-area pole triangles (two coinciding corners), 2 views, vi [F,3]
   multi_  per-view topology vi [N,F,3]: a face that lists a vertex twice, an unreferenced vertex
+  seam_   (archives of its own, refpy_geometry_seam_{f32,f64}.npz) the band of sphere(5, 6) with a latitude / longitude
+          atlas that has one more column of UV vertices than the mesh (the construction of drtk_amd.synthetic.
+          uv_sphere_atlas): T = V + n_lat + 1 and vti != vi, vt perturbed per view, 2 views; the keys of band_
 Per mesh: the inputs, the outputs of face_info / vert_normals (also with given fnorms) / face_attribute_to_vert
 (/ face_dpdt / vert_binormals), and their VJPs for stored upstream gradients (g_*)."""
+import argparse
 import math
 import os
 import sys
@@ -36,6 +41,20 @@ def sphere(n_lat, n_lon, poles):
     v00, v01, v10, v11 = ii * n_lon + jj, ii * n_lon + jn, (ii + 1) * n_lon + jj, (ii + 1) * n_lon + jn
     vi = np.stack([np.stack([v00, v10, v11], -1), np.stack([v00, v11, v01], -1)], 2).reshape(-1, 3)
     return v, vt, vi
+
+
+def atlas(n_lat, n_lon):
+    """The latitude / longitude atlas of sphere(n_lat, n_lon, .) with a column of UV vertices more than the mesh has, so that
+    the last column of quads runs to u = 1 instead of wrapping around (drtk_amd.synthetic.uv_sphere_atlas' construction):
+    (vt [(n_lat+1)*(n_lon+1), 2] float64, vti [F,3]), the faces in the order of sphere's vi"""
+    i, j = np.arange(n_lat + 1, dtype=np.float64), np.arange(n_lon + 1, dtype=np.float64)
+    w, u = np.meshgrid(0.02 + 0.96 * i / n_lat, 0.02 + 0.96 * j / n_lon, indexing="ij")
+    vt = np.stack([u, w], -1).reshape(-1, 2)
+    ii, jj = np.meshgrid(np.arange(n_lat), np.arange(n_lon), indexing="ij")
+    s = n_lon + 1
+    v00, v01, v10, v11 = ii * s + jj, ii * s + jj + 1, (ii + 1) * s + jj, (ii + 1) * s + jj + 1
+    vti = np.stack([np.stack([v00, v10, v11], -1), np.stack([v00, v11, v01], -1)], 2).reshape(-1, 3)
+    return vt, vti
 
 
 def views(v, n, rng, scale=0.05):
@@ -107,11 +126,35 @@ def run(drtk, dtype, name, v, vi, vt=None, vti=None, seed=0):
     return {f"{name}_{k}": (a.astype(np.float32) if dtype == th.float32 and a.dtype == np.float64 else a) for k, a in out.items()}
 
 
+def seam_mesh():
+    """(v [2,V,3], vi [F,3], vt [2,T,2], vti [F,3]) of seam_, from a generator of its own"""
+    rng = np.random.default_rng(11)
+    n_lat, n_lon = 5, 6
+    v, _, vi = sphere(n_lat, n_lon, poles=False)
+    vt, vti = atlas(n_lat, n_lon)
+    assert vt.shape[0] == v.shape[0] + n_lat + 1 and vti.shape == vi.shape and not np.array_equal(vti, vi)
+    return views(v, 2, rng), vi, np.stack([vt, vt + 0.01 * rng.standard_normal(vt.shape)]), vti
+
+
+def write(tag, arrays):
+    path = os.path.join(OUT, f"refpy_geometry_{tag}.npz")
+    np.savez_compressed(path, **arrays)
+    print(f"wrote {path} ({os.path.getsize(path)} bytes, {len(arrays)} arrays)")
+
+
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--seam-only", action="store_true", help="write refpy_geometry_seam_{f32,f64}.npz and leave the other two archives alone")
+    only_seam = ap.parse_args().seam_only
     th.set_num_threads(1)
     from gen_golden_refpy import import_reference
 
     drtk = import_reference()
+    seam = seam_mesh()
+    for dtype, tag in ((th.float32, "f32"), (th.float64, "f64")):
+        write(f"seam_{tag}", run(drtk, dtype, "seam", *seam, seed=4))
+    if only_seam:
+        return
     rng = np.random.default_rng(7)
     v, vt, vi = sphere(6, 8, poles=False)
     band = (views(v, 2, rng), vi, np.stack([vt, vt + 0.01 * rng.standard_normal(vt.shape)]), vi)
@@ -125,9 +168,7 @@ def main():
         arrays.update(run(drtk, dtype, "band", *band, seed=1))
         arrays.update(run(drtk, dtype, "poles", *poles, seed=2))
         arrays.update(run(drtk, dtype, "multi", vm, vim, seed=3))
-        path = os.path.join(OUT, f"refpy_geometry_{tag}.npz")
-        np.savez_compressed(path, **arrays)
-        print(f"wrote {path} ({os.path.getsize(path)} bytes, {len(arrays)} arrays)")
+        write(tag, arrays)
 
 
 if __name__ == "__main__":

@@ -13,8 +13,10 @@ The first case shows that a damaged guard is reported.  The image losses run the
 257, 297 and 513 partial sums in the slot workspace, whose size drtk_amd_image_loss_workspace_bytes gave), both precisions
 and paddings, plain and weighted, forward with the gradient maps and backward; mipmap_pyramid the ragged shapes of its test
 module at full depth, every level and grad_input element-aligned at once, with all gradients and with one absent; then the
-first 20 seeds of tests/fuzz_image_ops.py and the first 20 of tests/fuzz_added_ops.py (filter2d, composite_layers, shade,
-mesh_laplacian and msi on random shapes, layouts and options).  Oracles, bounds and helpers are those of the operators' own test
+first 20 seeds of tests/fuzz_image_ops.py, the first 20 of tests/fuzz_added_ops.py (filter2d, composite_layers, shade,
+mesh_laplacian and msi on random shapes, layouts and options) and the first 20 of tests/fuzz_geometry.py (the geometry entry
+points on random meshes, UV topologies of their own and partial chunks; the fixed geometry cases are the four fixture
+meshes, `seam` with its own UV topology among them).  Oracles, bounds and helpers are those of the operators' own test
 modules, which this script imports.  Left out: what the torch operators allocate in C++ (only the binding has guards) and
 grad_grid of grid_scatter (allocated with the grid's strides, outside `_out`)."""
 import argparse
@@ -146,8 +148,8 @@ def geometry_case(name):
     import test_gpu_geometry as T
 
     d32, d64 = T._load("f32"), T._load("f64")
-    got64 = T._run_all_capi(d64, name, F64, DEV)
-    got32 = T._run_all_capi(d32, name, F32, DEV)
+    got64 = T._run_all_capi(T._fixture_case(d64, name), F64, DEV)
+    got32 = T._run_all_capi(T._fixture_case(d32, name), F32, DEV)
     T._check_against_the_fixtures(name, got64, got32, d32, d64)
 
 
@@ -214,6 +216,16 @@ def fuzz_added_ops_case(seed):
         raise AssertionError(f"{F.describe(c)}: {e}") from e
 
 
+def fuzz_geometry_case(seed):
+    import fuzz_geometry as F
+
+    c = F.make_case(seed)
+    try:
+        F.run_case(c, check_guards=False)  # they are checked, and counted, after the case
+    except AssertionError as e:
+        raise AssertionError(f"{F.describe(c)}: {e}") from e
+
+
 def cases():
     """[(name, function, arguments)], in the order they run"""
     import image_loss_oracle
@@ -257,6 +269,8 @@ def cases():
         out.append((f"fuzz_image_ops/seed{seed}", fuzz_image_ops_case, (seed,)))
     for seed in range(20):
         out.append((f"fuzz_added_ops/seed{seed}", fuzz_added_ops_case, (seed,)))
+    for seed in range(20):
+        out.append((f"fuzz_geometry/seed{seed}", fuzz_geometry_case, (seed,)))
     assert len({c[0] for c in out}) == len(out)
     return out
 

@@ -1,7 +1,7 @@
 """CPU: the mesh geometry of drtk.utils (face_info, vert_normals, face_attribute_to_vert, face_dpdt, vert_binormals,
 index) -- names and signatures of the reference, the PyTorch formulation against the reference's own outputs and
-VJPs (tests/golden/refpy_geometry_*.npz, written by tests/gen_golden_geometry.py), the C ABI's argument checks and the
-incidence builders."""
+VJPs (tests/golden/refpy_geometry_*.npz, written by tests/gen_golden_geometry.py; `seam` with a UV topology of its own),
+the C ABI's argument checks and the incidence builders."""
 import ctypes
 import inspect
 import os
@@ -13,12 +13,30 @@ from conftest import ROOT
 
 from f64_distance import assert_within_f64_distance
 
-NAMES = ("band", "poles", "multi")
+NAMES = ("band", "poles", "multi", "seam")
 
 
 def _load(tag):
-    z = np.load(os.path.join(ROOT, "tests", "golden", f"refpy_geometry_{tag}.npz"))
-    return {k: th.from_numpy(z[k]) for k in z.files}
+    """the three meshes of refpy_geometry_<tag>.npz and the seam mesh of refpy_geometry_seam_<tag>.npz, in one dict"""
+    d = {}
+    for stem in (f"refpy_geometry_{tag}", f"refpy_geometry_seam_{tag}"):
+        z = np.load(os.path.join(ROOT, "tests", "golden", stem + ".npz"))
+        d.update({k: th.from_numpy(z[k]) for k in z.files})
+    return d
+
+
+def test_the_seam_fixture_has_a_uv_topology_of_its_own():
+    """vti != vi and T = V + n_lat + 1 (a column of UV vertices more than the mesh has), every UV vertex used, and a vertex of
+    the mesh's first column listed under two UV vertices: what makes face_dpdt / vert_binormals with the position incidence
+    in place of the UV one, or V in place of T, fail on this fixture."""
+    d = _load("f64")
+    vi, vti = d["seam_vi"].long(), d["seam_vti"].long()
+    V, T = d["seam_v"].shape[1], d["seam_vt"].shape[1]
+    assert vi.shape == vti.shape == (60, 3) and (V, T) == (36, 42) and not th.equal(vi, vti)
+    assert th.equal(vti.unique(), th.arange(T)) and th.equal(vi.unique(), th.arange(V))
+    pairs = {(int(a), int(b)) for a, b in zip(vi.reshape(-1), vti.reshape(-1))}
+    assert max(sum(1 for a, _ in pairs if a == vert) for vert in range(V)) == 2
+    assert d["seam_vt"].shape[0] == 2 and not th.equal(d["seam_vt"][0], d["seam_vt"][1])
 
 
 def test_drop_in_names_resolve_and_project_points_grad_stays_out():

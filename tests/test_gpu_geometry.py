@@ -1,7 +1,11 @@
 """GPU: the mesh geometry of drtk.utils on the HIP route (csrc/geometry.hip through the drtk_amd_ext operators and the
-C ABI) -- against the reference's outputs and VJPs (tests/golden/refpy_geometry_*.npz), against the float64 PyTorch
-formulation at full size, bitwise reproducibility, the incidence cache, graph capture, a shading step end to end, and
-the shapes that stress the vertex pass (a 65 536-valence fan, 70 000 views, no faces)."""
+C ABI) -- against the reference's outputs and VJPs (tests/golden/refpy_geometry_*.npz: three meshes with vti = vi and
+`seam`, whose UV atlas has a topology of its own, T = V + 6 UV vertices), through the operators and through the C ABI
+composed by _run_all_capi, against the float64 PyTorch formulation at full size, bitwise reproducibility, the incidence
+cache, graph capture, a shading step end to end, and the shapes that stress the vertex pass (a 65 536-valence fan,
+70 000 views, no faces).  The helpers that take tensors -- _run_all_capi, _near_degenerate, _split, check_float64,
+check_float32 -- and their bounds are also those of the seeded random cases of tests/fuzz_geometry.py
+(tests/test_gpu_fuzz_geometry.py), which states no bound of its own."""
 import os
 
 import numpy as np
@@ -14,12 +18,16 @@ from f64_distance import assert_within_f64_distance
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
-NAMES = ("band", "poles", "multi")
+NAMES = ("band", "poles", "multi", "seam")
 
 
 def _load(tag):
-    z = np.load(os.path.join(ROOT, "tests", "golden", f"refpy_geometry_{tag}.npz"))
-    return {k: th.from_numpy(z[k]) for k in z.files}
+    """the three meshes of refpy_geometry_<tag>.npz and the seam mesh of refpy_geometry_seam_<tag>.npz, in one dict"""
+    d = {}
+    for stem in (f"refpy_geometry_{tag}", f"refpy_geometry_seam_{tag}"):
+        z = np.load(os.path.join(ROOT, "tests", "golden", stem + ".npz"))
+        d.update({k: th.from_numpy(z[k]) for k in z.files})
+    return d
 
 
 def _run_all(d, name, dtype, idx_dtype, dev):
@@ -66,12 +74,12 @@ _FACE_C = ("face_info_normals",)
 _VERT_C = ("face_info_grad_v", "vert_normals", "vert_normals_grad_v")
 
 
-def _near_degenerate(d64, name):
-    """(faces [N,F] with |c| < 1e-8 in the reference, vertices [N,V] that touch one)"""
-    faces = (2 * d64[f"{name}_face_info_areas"][..., 0]) < 1e-8
-    N, V = d64[f"{name}_v"].shape[:2]
-    vi = d64[f"{name}_vi"].long()
-    vi = vi[None].expand(N, -1, -1) if vi.dim() == 2 else vi
+def _near_degenerate(areas, vi, V):
+    """(faces [N,F] with |c| < 1e-8 in the reference's areas [N,F,1], vertices [N,V] that touch one through vi)"""
+    faces = (2 * areas[..., 0]) < 1e-8
+    N = areas.shape[0]
+    vi = vi.long()
+    vi = vi.expand(N, -1, -1) if vi.dim() == 3 else vi[None].expand(N, -1, -1)
     verts = th.zeros(N, V, dtype=th.bool)
     for n in range(N):
         verts[n, vi[n][faces[n]].reshape(-1)] = True
@@ -102,26 +110,37 @@ def test_hip_route_matches_the_reference_fixtures(name, idx_dtype):
     _check_against_the_fixtures(name, got64, got32, d32, d64)
 
 
-def _run_all_capi(d, name, dtype, dev):
+def _fixture_case(d, name):
+    """The arrays of mesh `name` without their prefix: a case as _run_all_capi and check_float64 / check_float32 take it"""
+    return {k[len(name) + 1:]: t for k, t in d.items() if k.startswith(name + "_")}
+
+
+def _run_all_capi(case, dtype, dev):
     """What _run_all computes, composed from the four geometry entry points of the C ABI (int32 topology, the numpy
-    incidence) the way csrc/torch_ops/geometry.cpp composes them: {name: tensor on the CPU}, the same keys."""
+    incidence) the way csrc/torch_ops/geometry.cpp composes them: {name: tensor on the CPU}, the same keys.  `case`: the
+    inputs and upstream gradients under a fixture's names without the prefix (_fixture_case; tests/fuzz_geometry.py makes
+    its own) -- of g_face_info_{normals,areas,edges} those that are there, the outputs of face_info those that
+    `face_info_outputs` lists (default all three), face_dpdt and vert_binormals on `vi_shared` [F,3] where vi is one list
+    per view (default vi)."""
     from drtk_amd import capi
 
-    p = lambda k: d[f"{name}_{k}"].to(dev).clone()  # noqa: E731
-    g = lambda k: p(k).to(dtype)  # noqa: E731
+    p = lambda k: case[k].to(dev).clone()  # noqa: E731
+    g = lambda k: p(k).to(dtype) if k in case else None  # noqa: E731
     vi = p("vi").to(th.int32)
     v = g("v")
     V = v.shape[1]
     inc = capi.vertex_incidence_numpy(vi.cpu().numpy(), V)
     to_v = lambda rows: capi.geometry_vertex_gather(rows, inc, V, per_corner=True)[0]  # noqa: E731
     res = {}
-    f = capi.geometry_face_forward(v, vi, outputs=("normals", "areas", "edges"))
-    res.update({f"face_info_{k}": f[k] for k in ("normals", "areas", "edges")})
+    kinds = tuple(case.get("face_info_outputs", ("normals", "areas", "edges")))
+    f = capi.geometry_face_forward(v, vi, outputs=kinds)
+    res.update({f"face_info_{k}": f[k] for k in kinds})
     pos, uv = capi.geometry_face_backward(v, vi, grad_normals=g("g_face_info_normals"), grad_areas=g("g_face_info_areas"),
                                           grad_edges=g("g_face_info_edges"))
     assert uv is None
     res["face_info_grad_v"] = to_v(pos)
-    vn, sums = capi.geometry_vertex_gather(f["normals"], inc, V, normalize=True)
+    normals = f["normals"] if "normals" in kinds else capi.geometry_face_forward(v, vi, outputs=("normals",))["normals"]
+    vn, sums = capi.geometry_vertex_gather(normals, inc, V, normalize=True)
     pos, _ = capi.geometry_face_backward(v, vi, grad_vert=g("g_vert_normals"), vert_sums=sums)
     res["vert_normals"], res["vert_normals_grad_v"] = vn, to_v(pos)
     vnf, sums = capi.geometry_vertex_gather(g("fnorms"), inc, V, normalize=True)
@@ -131,7 +150,10 @@ def _run_all_capi(d, name, dtype, dev):
     assert none is None
     res["face_attribute_to_vert"] = fv
     res["face_attribute_to_vert_grad_attr"] = capi.geometry_face_gather(g("g_face_attribute_to_vert"), vi)
-    if f"{name}_vt" in d:
+    if "vt" in case:
+        if "vi_shared" in case:
+            vi = p("vi_shared").to(th.int32)
+            inc = capi.vertex_incidence_numpy(vi.cpu().numpy(), V)
         vti, vt = p("vti").to(th.int32), g("vt")
         T = vt.shape[1]
         tinc = capi.vertex_incidence_numpy(vti.cpu().numpy(), T)
@@ -145,27 +167,51 @@ def _run_all_capi(d, name, dtype, dev):
     return {k: t.detach().cpu() for k, t in res.items()}
 
 
+def check_float64(k, got, ref, faces, verts, what):
+    """Output or gradient `k` of a float64 run against the float64 reference: within 1e-9 of the output's scale; entries
+    behind a face with |c| < 1e-8 (`faces`, `verts` of _near_degenerate): finite, and a face normal that is exactly 0 in
+    the reference exactly 0."""
+    (a, a_deg), (b, b_deg) = _split(k, got, faces, verts), _split(k, ref, faces, verts)
+    err = float((a - b).abs().max()) if a.numel() else 0.0
+    assert err <= 1e-9 * max(1.0, float(b.abs().max()) if b.numel() else 0.0), (what, k, err)
+    assert bool(th.isfinite(a_deg).all()), (what, k)
+    exact = b_deg == 0
+    assert th.equal(a_deg[exact], b_deg[exact]) or k not in _FACE_C, (what, k)
+
+
+def check_float32(k, got, ref32, ref64, faces, verts, what):
+    """The same of a float32 run: the entries not behind such a face within the f64-distance bound (its defaults), the others
+    finite"""
+    ok = [_split(k, x, faces, verts)[0] for x in (got, ref32, ref64)]
+    assert_within_f64_distance(*ok, f"{what} {k}")
+    assert bool(th.isfinite(_split(k, got, faces, verts)[1]).all()), (what, k)
+
+
 def _check_against_the_fixtures(name, got64, got32, d32, d64):
     """The bounds of test_hip_route_matches_the_reference_fixtures (its docstring), on what _run_all or _run_all_capi gave."""
-    faces, verts = _near_degenerate(d64, name)
+    faces, verts = _near_degenerate(d64[f"{name}_face_info_areas"], d64[f"{name}_vi"], d64[f"{name}_v"].shape[1])
     for k, t in got64.items():
-        ref = d64[f"{name}_{k}"]
-        (a, a_deg), (b, b_deg) = _split(k, t, faces, verts), _split(k, ref, faces, verts)
-        err = float((a - b).abs().max()) if a.numel() else 0.0
-        assert err <= 1e-9 * max(1.0, float(b.abs().max()) if b.numel() else 0.0), (name, k, err)
-        assert bool(th.isfinite(a_deg).all()), (name, k)
-        exact = b_deg == 0
-        assert th.equal(a_deg[exact], b_deg[exact]) or k not in _FACE_C, (name, k)
+        check_float64(k, t, d64[f"{name}_{k}"], faces, verts, name)
     assert got32.keys() == got64.keys()
     for k, t in got32.items():
-        ok = [_split(k, x, faces, verts)[0] for x in (t, d32[f"{name}_{k}"], d64[f"{name}_{k}"])]
-        assert_within_f64_distance(*ok, f"{name} {k}")
+        check_float32(k, t, d32[f"{name}_{k}"], d64[f"{name}_{k}"], faces, verts, name)
     if name == "multi":
         # its degenerate faces list a vertex twice: c is exactly 0 and the 1e8 branch is taken exactly; a vertex listed
         # twice receives two 1e8-scaled corner rows that cancel, so it is held to double rounding at that scale
         for k in _VERT_C:
             a, b = got64[k][verts], d64[f"{name}_{k}"][verts]
             assert float((a - b).abs().max()) <= 1e-15 * 1e8 * 10 * max(1.0, float(b.abs().max())), k
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_c_abi_composition_matches_the_reference_fixtures(name):
+    """The same fixtures through the four entry points of the C ABI, composed by _run_all_capi (which tests/fuzz_geometry.py
+    and tests/guarded_added_ops.py use): the bounds of the operators' test above."""
+    d32, d64 = _load("f32"), _load("f64")
+    got64 = _run_all_capi(_fixture_case(d64, name), th.float64, DEV)
+    got32 = _run_all_capi(_fixture_case(d32, name), th.float32, DEV)
+    assert set(got64) == {k[len(name) + 1:] for k in d64 if k.startswith(name + "_") and (k[len(name) + 1:].split("_")[0] in ("face", "vert"))}
+    _check_against_the_fixtures(name, got64, got32, d32, d64)
 
 
 def _sphere_views(n, size, dtype=th.float32, dev=DEV):
