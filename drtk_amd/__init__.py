@@ -33,6 +33,7 @@ from drtk_amd.interpolate import (  # noqa: F401
     interpolation_matrix,
     interpolation_normal_matrix,
 )
+from drtk_amd.kinematics import forward_kinematics  # noqa: F401
 from drtk_amd.mipmap_grid_sample import mipmap_grid_sample  # noqa: F401
 from drtk_amd.mipmap_pyramid import mipmap_pyramid  # noqa: F401
 from drtk_amd.msi import msi  # noqa: F401
@@ -68,7 +69,10 @@ __version__ = "0.1.0"
 # Lambert, ambient, highlight, background select and gamma in one fused pass each way, the parameter gradients summed in a
 # fixed order) is an addition of the same kind and stays out of the drop-in as well.  `skin` (linear blend skinning, the
 # step from rig parameters to geometry: forward and the gradients to the rest pose, the weights and the joint transforms,
-# no float atomics) with its companion `sparse_skin_weights` is one more, and stays out of the drop-in too.  `transform` / `transform_with_v_cam` serve the pinhole camera and, on the HIP device, the reference's
+# no float atomics) with its companion `sparse_skin_weights` is one more, and stays out of the drop-in too.
+# `forward_kinematics` (the step before it: axis-angle or matrix pose along a joint tree to the skinning matrices `skin`
+# reads and the posed joints, one launch each way, the exponential map smooth at 0) is the latest, and stays out of the
+# drop-in as well.  `transform` / `transform_with_v_cam` serve the pinhole camera and, on the HIP device, the reference's
 # distortion models (radial-tangential, fisheye, fisheye62 with its lookup table, per-view lists) in one fused kernel each
 # way; the field-of-view estimators live in drtk_amd.transform (`estimate_rt_fov`, `estimate_fisheye_fov`,
 # `estimate_fisheye62_fov`) and in the drop-in's drtk.utils.  Not provided: the pure-PyTorch `*_ref` models (out of scope).
@@ -114,4 +118,5 @@ __all__ = [
     "mesh_laplacian",
     "skin",
     "sparse_skin_weights",
+    "forward_kinematics",
 ]

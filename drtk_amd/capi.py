@@ -182,6 +182,9 @@ EXPORTS = [
     "drtk_amd_skin_forward",
     "drtk_amd_skin_backward_workspace_bytes",
     "drtk_amd_skin_backward",
+    "drtk_amd_kinematics_forward",
+    "drtk_amd_kinematics_backward_workspace_bytes",
+    "drtk_amd_kinematics_backward",
     "drtk_amd_selftest_exact_div",
     "drtk_amd_kernel_timing_begin",
     "drtk_amd_kernel_timing_report",
@@ -1383,6 +1386,102 @@ def skin_backward(grad_out, v, joint_idx, joint_weights, transforms, incidence=N
             _stream(v, stream)),
         "skin_backward")
     return gv, gw, gt
+
+
+FK_MAX_JOINTS = 320  # DRTK_FK_MAX_JOINTS of include/drtk_amd.h
+
+
+def kinematic_schedule_numpy(parents):
+    """The schedule drtk_amd_kinematics_* take (include/drtk_amd.h, "Forward kinematics"), built with numpy from `parents`
+    [J] (-1: a root, else 0 <= parents[j] < j): (parents, order [J], level_start [D+1], child_crow [J+1], child_entries),
+    int32.  `order` lists the joints by (depth, index); a joint's children are ascending."""
+    import numpy as np
+
+    p = np.asarray(parents)
+    if p.ndim != 1 or p.dtype.kind not in "iu":
+        raise ValueError("parents: expected a one-dimensional integer array")
+    p = p.astype(np.int64)
+    J = p.size
+    if J and not ((p >= -1) & (p < np.arange(J))).all():
+        raise ValueError("parents: expected parents[j] == -1 (a root) or 0 <= parents[j] < j")
+    depth = np.zeros(J, dtype=np.int64)
+    for j in range(J):
+        depth[j] = 0 if p[j] < 0 else depth[p[j]] + 1
+    order = np.argsort(depth, kind="stable")
+    D = int(depth.max()) + 1 if J else 0
+    level_start = np.searchsorted(depth[order], np.arange(D + 1), side="left")
+    kids = np.nonzero(p >= 0)[0]
+    child_entries = kids[np.argsort(p[kids], kind="stable")]
+    child_crow = np.searchsorted(p[child_entries], np.arange(J + 1), side="left")
+    return tuple(a.astype(np.int32) for a in (p, order, level_start, child_crow, child_entries))
+
+
+def _kinematics_args(rotations, joints, translation, schedule):
+    """-> (rot_is_matrix, strides array, joints contiguous, c_sN, translation, schedule tensors on the device, N, J, D)"""
+    assert rotations.dim() in (3, 4) and rotations.shape[2:] in ((3,), (3, 3)), rotations.shape
+    N, J = rotations.shape[0], rotations.shape[1]
+    mat = rotations.dim() == 4
+    st = list(rotations.stride()) + ([0] if not mat else [])
+    strides = (ctypes.c_int64 * 4)(*st)
+    assert joints.dtype == rotations.dtype and joints.shape in ((J, 3), (1, J, 3), (N, J, 3)), joints.shape
+    c = joints.reshape(-1, J, 3).contiguous()
+    c_sN = 0 if c.shape[0] == 1 else 3 * J  # (one view: one row either way)
+    if translation is not None:
+        assert translation.shape == (N, 3) and translation.dtype == rotations.dtype
+        translation = translation.contiguous()
+    sch = [th.as_tensor(a, dtype=th.int32, device=rotations.device).contiguous() for a in schedule]
+    assert sch[0].numel() == J and sch[1].numel() == J and sch[3].numel() == J + 1
+    D = sch[2].numel() - 1
+    return int(mat), strides, c, c_sN, translation, sch, N, J, D
+
+
+@_on_tensor_device
+def kinematics_forward(rotations, joints, schedule, translation=None, stream=None):
+    """(transforms [N,J,3,4], posed_joints [N,J,3]) of rotations [N,J,3] / [N,J,3,3] (read through their strides), joints
+    [J,3] / [1,J,3] (shared) or [N,J,3], `schedule` = kinematic_schedule_numpy(parents) and translation [N,3] or None."""
+    mat, strides, c, c_sN, tr, sch, N, J, D = _kinematics_args(rotations, joints, translation, schedule)
+    out_t = _out(N, J, 3, 4, dtype=rotations.dtype, device=rotations.device)
+    out_p = _out(N, J, 3, dtype=rotations.dtype, device=rotations.device)
+    _check(lib().drtk_amd_kinematics_forward(ctypes.c_int(_dt(rotations)), _p(rotations), ctypes.c_int(mat), strides, _p(c), _i(c_sN),
+                                             _p(tr), _p(sch[0]), _p(sch[1]), _p(sch[2]), _i(D), _i(N), _i(J), _p(out_t), _p(out_p),
+                                             _stream(rotations, stream)), "kinematics_forward")
+    return out_t, out_p
+
+
+def kinematics_backward_workspace_bytes(dtype, N, J, grad_joints_B) -> int:
+    out = ctypes.c_size_t(0)
+    code = DRTK_F32 if dtype == th.float32 else DRTK_F64
+    _check(lib().drtk_amd_kinematics_backward_workspace_bytes(ctypes.c_int(code), _i(N), _i(J), _i(grad_joints_B), ctypes.byref(out)),
+           "kinematics_backward")
+    return out.value
+
+
+@_on_tensor_device
+def kinematics_backward(grad_transforms, grad_posed, rotations, joints, schedule, translation=None,
+                        grads=("rotations", "joints", "translation"), stream=None):
+    """(grad_rotations, grad_joints, grad_translation) of kinematics_forward, None for what `grads` does not name (and
+    grad_translation without a translation).  Either of grad_transforms / grad_posed may be None (zero).  grad_joints is
+    [1,J,3] (the views' rows added, n ascending, in double) where the joints were given as one row, else [N,J,3]."""
+    mat, strides, c, c_sN, tr, sch, N, J, D = _kinematics_args(rotations, joints, translation, schedule)
+    dt, dev = rotations.dtype, rotations.device
+    gA = None if grad_transforms is None else grad_transforms.contiguous()
+    gP = None if grad_posed is None else grad_posed.contiguous()
+    assert gA is None or (gA.shape == (N, J, 3, 4) and gA.dtype == dt)
+    assert gP is None or (gP.shape == (N, J, 3) and gP.dtype == dt)
+    gr = _out(*rotations.shape, dtype=dt, device=dev) if "rotations" in grads else None
+    gc_B = 1 if c_sN == 0 else N
+    gc = _out(gc_B, J, 3, dtype=dt, device=dev) if "joints" in grads else None
+    gt = _out(N, 3, dtype=dt, device=dev) if "translation" in grads and tr is not None else None
+    need = kinematics_backward_workspace_bytes(dt, N, J, gc_B if gc is not None else 0)
+    ws = _out(max(need, 1), dtype=th.uint8, device=dev)
+    assert ws.data_ptr() % 8 == 0
+    _check(
+        lib().drtk_amd_kinematics_backward(
+            ctypes.c_int(_dt(rotations)), _p(gA), _p(gP), _p(rotations), ctypes.c_int(mat), strides, _p(c), _i(c_sN), _p(tr),
+            _p(sch[0]), _p(sch[1]), _p(sch[2]), _i(D), _p(sch[3]), _p(sch[4]), _i(N), _i(J), _p(gr), _i(gc_B), _p(gc), _p(gt),
+            _p(ws), ctypes.c_size_t(need), _stream(rotations, stream)),
+        "kinematics_backward")
+    return gr, gc, gt
 
 
 def edge_grad_backward_workspace_bytes(dtype, N, H, W) -> int:

@@ -779,6 +779,54 @@ int drtk_amd_skin_backward(
     int64_t num_chunks, int64_t N, int64_t V, int64_t J, int64_t K, int64_t grad_v_B, void* grad_v, void* grad_weights,
     int64_t grad_t_rows, void* grad_transforms, void* workspace, size_t workspace_bytes, drtk_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Forward kinematics along a joint tree (no counterpart in the reference's library): from the pose to the skinning
+ * matrices drtk_amd_skin_forward reads and the posed joints, and the gradients, without atomics.  With p = parents[j]
+ * (-1: a root; else 0 <= p < j), R_j the local rotation and c_j the rest joint:
+ *     root:   G_j.R = R_j              G_j.t = c_j + translation[n]
+ *     child:  G_j.R = G_p.R R_j        G_j.t = G_p.R (c_j - c_p) + G_p.t
+ *     posed_joints[n,j] = G_j.t        transforms[n,j] = [ G_j.R | G_j.t - G_j.R c_j ]      ([N,J,3,4], [N,J,3], contiguous)
+ *
+ * rotations: rot_is_matrix = 0: axis-angle vectors, component a of joint j of view n at n*rot_strides[0] + j*rot_strides[1] +
+ * a*rot_strides[2] (rot_strides[3] is not read); R = I + a K + b K^2 with K the skew matrix of r, t2 = r.r, a = sin(t)/t,
+ * b = (1/2) (sin(t/2) / (t/2))^2; for t2 below 1/16 (float32) or 1/256 (float64) a, b and their derivatives are five-term
+ * Taylor series in t2, so r = 0 gives I and the finite gradient of the exponential map.  No wrapping of angles.
+ * rot_is_matrix = 1: 3x3 matrices used as given, element (a,b) at ... + a*rot_strides[2] + b*rot_strides[3].  Strides in
+ * elements, any values.  joints: [J,3] shared by the views (c_sN = 0) or [N,J,3] (c_sN = 3J), rows contiguous.
+ * translation: [N,3] or NULL.
+ *
+ * The SCHEDULE of `parents`, built by the caller once per tree (drtk_amd_ext::kinematic_schedule builds and caches it;
+ * drtk_amd/capi.py has a numpy builder); the kernels trust it and `parents`:
+ *     order         int32 [J]     the joints sorted by (depth, index)
+ *     level_start   int32 [D+1]   level l is order[level_start[l] .. level_start[l+1]-1]; num_levels = D (level 0: the roots)
+ *     child_crow    int32 [J+1]   joint j's children are child_entries[child_crow[j] .. child_crow[j+1]-1], ASCENDING
+ *     child_entries int32 [J - number of roots]
+ *
+ * One workgroup of 64 lanes per view holds every joint's 3x4 in LDS: J <= DRTK_FK_MAX_JOINTS, above which the entry points
+ * return DRTK_ERR_INVALID_ARGUMENT.  320: the backward keeps two arrays of 12 values per joint, 2 * 12 * 8 bytes * 320 =
+ * 61440 bytes of double, inside the 65536 bytes a workgroup may declare statically.
+ *
+ * kinematics_backward: grad_transforms [N,J,3,4] and grad_posed [N,J,3], either may be NULL (zero).  NULL outputs are
+ * skipped, at least one must be given.  grad_rotations [N,J,3] or [N,J,3,3] (the plain matrix gradient), contiguous;
+ * grad_joints [grad_joints_B,J,3], grad_joints_B = N, or 1: the views' rows, written to the workspace of _workspace_bytes
+ * (8-byte aligned; 0 bytes when N = 1), are added in ascending n in double by a second launch; grad_translation [N,3]: the
+ * roots' gradients added in ascending index.  A joint adds its children's terms in child_entries order.  Results are
+ * bitwise reproducible, and each gradient requested alone has the bits it has when all are requested.
+ */
+#define DRTK_FK_MAX_JOINTS 320
+int drtk_amd_kinematics_forward(
+    drtk_dtype_t dtype, const void* rotations, int rot_is_matrix, const int64_t* rot_strides, const void* joints,
+    int64_t c_sN, const void* translation, const int32_t* parents, const int32_t* order, const int32_t* level_start,
+    int64_t num_levels, int64_t N, int64_t J, void* transforms, void* posed_joints, drtk_stream_t stream);
+int drtk_amd_kinematics_backward_workspace_bytes(drtk_dtype_t dtype, int64_t N, int64_t J, int64_t grad_joints_B,
+                                                 size_t* bytes);
+int drtk_amd_kinematics_backward(
+    drtk_dtype_t dtype, const void* grad_transforms, const void* grad_posed, const void* rotations, int rot_is_matrix,
+    const int64_t* rot_strides, const void* joints, int64_t c_sN, const void* translation, const int32_t* parents,
+    const int32_t* order, const int32_t* level_start, int64_t num_levels, const int32_t* child_crow,
+    const int32_t* child_entries, int64_t N, int64_t J, void* grad_rotations, int64_t grad_joints_B, void* grad_joints,
+    void* grad_translation, void* workspace, size_t workspace_bytes, drtk_stream_t stream);
+
 /* Diagnostics: compares the rasterizer's reciprocal-based exact division with the IEEE `/` on `count`
  * pseudo-random operand pairs on the device; *d_mismatches (device memory) receives the number of
  * differing results (must be 0). */
