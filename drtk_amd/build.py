@@ -171,7 +171,7 @@ OPS_SRCS = ["rasterize.cpp", "render.cpp", "interpolate.cpp", "interp_matrix.cpp
 
 
 def _ops_deps():
-    return [os.path.join(OPS_DIR, f) for f in OPS_SRCS + ["common.hpp"]] + [os.path.join(INC, "drtk_amd.h"), LIB + ".src", __file__]
+    return [os.path.join(OPS_DIR, f) for f in OPS_SRCS + ["common.hpp", "topology_cache.hpp"]] + [os.path.join(INC, "drtk_amd.h"), LIB + ".src", __file__]
 
 
 def build_torch_ops(force=False, verbose=True):

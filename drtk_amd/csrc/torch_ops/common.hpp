@@ -10,11 +10,6 @@
 #include <torch/csrc/autograd/custom_function.h>
 #include <torch/library.h>
 
-#include <array>
-#include <list>
-#include <mutex>
-#include <unordered_map>
-
 #include "drtk_amd.h"
 
 namespace drtk_amd_torch {

@@ -2,6 +2,8 @@
 // drtk_amd_composite_layers_backward (include/drtk_amd.h).  No reference counterpart.  Host-only C++; the CPU key raises.
 #include "common.hpp"
 
+#include <array>
+
 namespace {
 using namespace drtk_amd_torch;
 using c10::optional;

@@ -4,6 +4,7 @@
 
 #include <cmath>
 #include <map>
+#include <mutex>
 #include <tuple>
 #include <vector>
 

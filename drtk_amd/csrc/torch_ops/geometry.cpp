@@ -2,9 +2,9 @@
 // face_attribute_to_vert, face_dpdt, vert_binormals) over drtk_amd_geometry_* (csrc/geometry.hip): a face pass and a
 // vertex pass that sums through the vertex incidence, each way, without float atomics.
 // Also this package's mesh regulariser on the same passes: cotangent_weights and mesh_laplacian.
-#include "common.hpp"
+#include "topology_cache.hpp"
 
-#include <hip/hip_runtime_api.h>
+#include <algorithm>
 
 namespace {
 using namespace drtk_amd_torch;
@@ -12,16 +12,15 @@ using namespace drtk_amd_torch;
 constexpr int64_t kChunk = DRTK_GEOMETRY_CHUNK;
 
 // ---------------------------------------------------------------------------------------------
-// Vertex incidence (CSR over rows b*V + vertex, entries f*3+k ascending within a row) and the chunk list of its long
-// rows, built where vi lives with ATen: stable sort of the keys b*V + vi[b,f,k] (the permutation is then ascending
-// within equal keys), searchsorted for the row starts.  One host read per build: the index range (an index outside
-// [0, V) would make the kernels read out of bounds) and the number of chunks (a launch size).
+// Vertex incidence: the chunked CSR (topology_cache.hpp) over rows b*V + vertex of the keys b*V + vi[b,f,k], entries
+// f*3+k ascending within a row, only the rows longer than DRTK_GEOMETRY_CHUNK cut into chunks.  An index outside [0, V)
+// would make the kernels read out of bounds.
 // ---------------------------------------------------------------------------------------------
 struct Incidence {
   Tensor vi32; // int32 [B,F,3] contiguous
-  Tensor crow, entries; // int32 [B*V+1], [3*B*F]
-  Tensor chunk_ptr, chunk_begin, chunk_row; // int32 [B*V+1], [C], [C]
-  int64_t B = 1, F = 0, V = 0, C = 0;
+  Tensor entries; // int32 [3*B*F]
+  ChunkedCsr csr; // rows B*V
+  int64_t B = 1, F = 0, V = 0;
 };
 
 Incidence build_incidence(const Tensor& t, int64_t V, const char* op) {
@@ -30,143 +29,21 @@ Incidence build_incidence(const Tensor& t, int64_t V, const char* op) {
   TORCH_CHECK(V >= 0 && V < (int64_t(1) << 31), op, "(): expected the vertex count to fit in int32");
   const int64_t R = inc.B * V, E = 3 * inc.B * inc.F;
   TORCH_CHECK(E < (int64_t(1) << 31) && R < (int64_t(1) << 31), op, "(): mesh too large for int32 incidence");
-  const auto iopts = t.options().dtype(at::kInt);
-  const auto lopts = t.options().dtype(at::kLong);
   const Tensor tl = t.detach().to(at::kLong).contiguous();
   inc.vi32 = t.detach().to(at::kInt).contiguous();
-  inc.chunk_begin = at::empty({0}, iopts);
-  inc.chunk_row = at::empty({0}, iopts);
-  if (E == 0) {
-    inc.crow = at::zeros({R + 1}, iopts);
-    inc.entries = at::empty({0}, iopts);
-    inc.chunk_ptr = at::zeros({R + 1}, iopts);
-    return inc;
-  }
-  const Tensor keys = (tl + (at::arange(inc.B, lopts) * V).view({-1, 1, 1})).reshape({-1});
-  const auto sorted = at::sort(keys, /*stable=*/true, /*dim=*/0, /*descending=*/false);
-  inc.entries = at::remainder(std::get<1>(sorted), 3 * inc.F).to(at::kInt);
-  const Tensor crow = at::searchsorted(std::get<0>(sorted), at::arange(R + 1, lopts));
-  inc.crow = crow.to(at::kInt);
-  const Tensor len = crow.narrow(0, 1, R) - crow.narrow(0, 0, R);
-  const Tensor nch = at::where(len > kChunk, at::floor_divide(len + (kChunk - 1), kChunk), at::zeros_like(len));
-  const Tensor cptr = at::cat({at::zeros({1}, lopts), at::cumsum(nch, 0)});
-  const auto mm = at::aminmax(tl);
-  const Tensor stats = at::stack({std::get<0>(mm).reshape({}), std::get<1>(mm).reshape({}), cptr[R]}).cpu();
-  const int64_t* s = stats.data_ptr<int64_t>();
-  TORCH_CHECK(s[0] >= 0 && s[1] < V, op, "(): vi contains a vertex index outside [0, ", V, ")");
-  inc.C = s[2];
-  inc.chunk_ptr = cptr.to(at::kInt);
-  if (inc.C > 0) {
-    const Tensor rows = at::repeat_interleave(nch, std::optional<int64_t>(inc.C)); // row of each chunk
-    const Tensor j = at::arange(inc.C, lopts) - cptr.index_select(0, rows);
-    inc.chunk_row = rows.to(at::kInt);
-    inc.chunk_begin = (crow.index_select(0, rows) + j * kChunk).to(at::kInt);
-  }
+  const Tensor keys = (tl + (at::arange(inc.B, tl.options()) * V).view({inc.B, 1, 1})).reshape({-1});
+  inc.csr = build_chunked_csr(keys, R, kChunk, /*chunk_every_row=*/false, tl);
+  TORCH_CHECK(E == 0 || (inc.csr.lo >= 0 && inc.csr.hi < V), op, "(): vi contains a vertex index outside [0, ", V, ")");
+  inc.entries = at::remainder(inc.csr.perm, std::max<int64_t>(3 * inc.F, 1)).to(at::kInt);
+  inc.csr.perm.reset();
   return inc;
 }
 
-// Cache: NormalMatrixPatternCache's key and pinning rules (interp_matrix.cpp) -- identity + version of the index
-// tensor, no content hashing; an in-place edit bumps the version counter and misses; each entry pins its vi so that a
-// recycled allocation cannot alias a stale entry; 128 entries, LRU.
-struct TopologyKey {
-  std::array<int64_t, 14> f;
-  bool operator==(const TopologyKey& o) const {
-    return f == o.f;
-  }
-};
-struct TopologyKeyHash {
-  size_t operator()(const TopologyKey& k) const {
-    uint64_t h = 1469598103934665603ull; // FNV-1a over the fields
-    for (int64_t x : k.f) {
-      h ^= static_cast<uint64_t>(x);
-      h *= 1099511628211ull;
-    }
-    return static_cast<size_t>(h);
-  }
-};
-TopologyKey topology_key(const Tensor& vi, int64_t num_vertices) {
-  TopologyKey k;
-  k.f = {static_cast<int64_t>(vi.device().type()),
-         static_cast<int64_t>(vi.device().index()),
-         static_cast<int64_t>(reinterpret_cast<uintptr_t>(vi.storage().unsafeGetStorageImpl())),
-         static_cast<int64_t>(reinterpret_cast<uintptr_t>(vi.data_ptr())),
-         vi.size(0),
-         vi.size(1),
-         vi.size(2),
-         vi.stride(0),
-         vi.stride(1),
-         vi.stride(2),
-         vi.storage_offset(),
-         static_cast<int64_t>(vi.scalar_type()),
-         num_vertices,
-         static_cast<int64_t>(vi.unsafeGetTensorImpl()->version_counter().current_version())};
-  return k;
+// Cached by the identity and version of the index tensor as incidence_of hands it over, and the vertex count.
+PinnedLruCache<Incidence>& incidence_cache() {
+  static PinnedLruCache<Incidence> c;
+  return c;
 }
-
-class IncidenceCache {
- public:
-  static constexpr size_t kCapacity = 128;
-  static IncidenceCache& instance() {
-    static IncidenceCache c;
-    return c;
-  }
-  Incidence get(const Tensor& vi, int64_t num_vertices, const char* op) {
-    const TopologyKey key = topology_key(vi, num_vertices);
-    {
-      std::lock_guard<std::mutex> lock(mu_);
-      if (const Incidence* hit = touch(key)) {
-        ++hits_;
-        return *hit;
-      }
-    }
-    if (vi.is_cuda()) {
-      // the build reads two numbers back and allocates: not capturable
-      hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-      const hipStream_t s = c10::hip::getCurrentHIPStream(vi.device().index()).stream();
-      TORCH_CHECK(hipStreamIsCapturing(s, &st) != hipSuccess || st == hipStreamCaptureStatusNone, op,
-                  "(): the vertex incidence of this index tensor is not cached yet, and it cannot be built while the "
-                  "stream is being captured -- run the op once with the same vi before the capture");
-    }
-    Incidence built = build_incidence(vi, num_vertices, op);
-    std::lock_guard<std::mutex> lock(mu_);
-    if (const Incidence* hit = touch(key)) return *hit;
-    ++misses_;
-    while (lru_.size() >= kCapacity) {
-      index_.erase(lru_.back().key);
-      lru_.pop_back();
-    }
-    lru_.push_front(Entry{key, vi, built});
-    index_.emplace(key, lru_.begin());
-    return built;
-  }
-  std::vector<int64_t> stats() {
-    std::lock_guard<std::mutex> lock(mu_);
-    return {hits_, misses_, static_cast<int64_t>(lru_.size())};
-  }
-  void clear() {
-    std::lock_guard<std::mutex> lock(mu_);
-    lru_.clear();
-    index_.clear();
-    hits_ = misses_ = 0;
-  }
-
- private:
-  struct Entry {
-    TopologyKey key;
-    Tensor pinned_vi;
-    Incidence inc;
-  };
-  const Incidence* touch(const TopologyKey& key) {
-    const auto it = index_.find(key);
-    if (it == index_.end()) return nullptr;
-    lru_.splice(lru_.begin(), lru_, it->second);
-    return &it->second->inc;
-  }
-  std::mutex mu_;
-  std::list<Entry> lru_;
-  std::unordered_map<TopologyKey, std::list<Entry>::iterator, TopologyKeyHash> index_;
-  int64_t hits_ = 0, misses_ = 0;
-};
 
 // vi [F,3] / [B,F,3] (B = 1 or N; a stride-0 expand counts as 1) -> its incidence over V vertices
 Incidence incidence_of(const Tensor& vi, int64_t N, int64_t V, const char* op) {
@@ -179,29 +56,29 @@ Incidence incidence_of(const Tensor& vi, int64_t N, int64_t V, const char* op) {
   if (t.size(0) > 1 && t.stride(0) == 0) t = t.narrow(0, 0, 1);
   TORCH_CHECK(t.size(0) == 1 || t.size(0) == N, op, "(): expected the batch size of vi to be 1 or ", N, ", got ",
               t.size(0));
-  return IncidenceCache::instance().get(t, V, op);
+  CacheKey key;
+  append_tensor_identity(key, t);
+  key.push_back(V);
+  return incidence_cache().get(key, t, [&] {
+    check_not_capturing(t.device(), op, "vertex incidence of this index tensor", "vi");
+    return build_incidence(t, V, op);
+  });
 }
 
 // Incidence tensors travel through autograd contexts as saved data
 void save_incidence(AutogradContext* ctx, const std::string& k, const Incidence& inc) {
   ctx->saved_data[k + "vi"] = inc.vi32;
-  ctx->saved_data[k + "crow"] = inc.crow;
   ctx->saved_data[k + "entries"] = inc.entries;
-  ctx->saved_data[k + "chunk_ptr"] = inc.chunk_ptr;
-  ctx->saved_data[k + "chunk_begin"] = inc.chunk_begin;
-  ctx->saved_data[k + "chunk_row"] = inc.chunk_row;
-  ctx->saved_data[k + "sizes"] = std::vector<int64_t>{inc.B, inc.F, inc.V, inc.C};
+  ctx->saved_data[k + "sizes"] = std::vector<int64_t>{inc.B, inc.F, inc.V};
+  inc.csr.save(ctx, k);
 }
 Incidence load_incidence(AutogradContext* ctx, const std::string& k) {
   Incidence inc;
   inc.vi32 = ctx->saved_data[k + "vi"].toTensor();
-  inc.crow = ctx->saved_data[k + "crow"].toTensor();
   inc.entries = ctx->saved_data[k + "entries"].toTensor();
-  inc.chunk_ptr = ctx->saved_data[k + "chunk_ptr"].toTensor();
-  inc.chunk_begin = ctx->saved_data[k + "chunk_begin"].toTensor();
-  inc.chunk_row = ctx->saved_data[k + "chunk_row"].toTensor();
   const auto s = ctx->saved_data[k + "sizes"].toIntVector();
-  inc.B = s[0], inc.F = s[1], inc.V = s[2], inc.C = s[3];
+  inc.B = s[0], inc.F = s[1], inc.V = s[2];
+  inc.csr = ChunkedCsr::load(ctx, k);
   return inc;
 }
 
@@ -228,15 +105,15 @@ Tensor vertex_gather(const Tensor& src, bool per_corner, int64_t A, const Incide
   Tensor s;
   if (sums) s = out_empty({N, inc.V, 3}, src.options());
   size_t bytes = 0;
-  check_status(drtk_amd_geometry_vertex_gather_workspace_bytes(dt, N, inc.B, inc.C, A, &bytes), op);
+  check_status(drtk_amd_geometry_vertex_gather_workspace_bytes(dt, N, inc.B, inc.csr.C, A, &bytes), op);
   Tensor ws = bytes ? alloc_workspace(bytes, src) : Tensor();
-  const bool chunks = inc.C > 0;
+  const bool chunks = inc.csr.C > 0;
   check_status(
       drtk_amd_geometry_vertex_gather(
-          dt, src.data_ptr(), inc.F * A * (per_corner ? 3 : 1), per_corner ? 1 : 0, A, inc.crow.data_ptr<int32_t>(),
-          inc.entries.data_ptr<int32_t>(), chunks ? inc.chunk_ptr.data_ptr<int32_t>() : nullptr,
-          chunks ? inc.chunk_begin.data_ptr<int32_t>() : nullptr, chunks ? inc.chunk_row.data_ptr<int32_t>() : nullptr,
-          inc.C, inc.B, N, inc.V, inc.F, normalize ? 1 : 0, out.data_ptr(), sums ? s.data_ptr() : nullptr,
+          dt, src.data_ptr(), inc.F * A * (per_corner ? 3 : 1), per_corner ? 1 : 0, A, inc.csr.crow.data_ptr<int32_t>(),
+          inc.entries.data_ptr<int32_t>(), chunks ? inc.csr.chunk_ptr.data_ptr<int32_t>() : nullptr,
+          chunks ? inc.csr.chunk_begin.data_ptr<int32_t>() : nullptr, chunks ? inc.csr.chunk_row.data_ptr<int32_t>() : nullptr,
+          inc.csr.C, inc.B, N, inc.V, inc.F, normalize ? 1 : 0, out.data_ptr(), sums ? s.data_ptr() : nullptr,
           ws.defined() ? ws.data_ptr() : nullptr, bytes, current_stream(src)),
       op);
   if (sums) *sums = s;
@@ -678,15 +555,15 @@ Tensor laplacian_apply(const Tensor& x, const Tensor& w, const Incidence& inc, c
   const int64_t N = x.size(0), C = x.size(2);
   auto out = out_empty({N, inc.V, C}, x.options());
   size_t bytes = 0;
-  check_status(drtk_amd_geometry_laplacian_workspace_bytes(dt, N, inc.B, inc.C, C, &bytes), op);
+  check_status(drtk_amd_geometry_laplacian_workspace_bytes(dt, N, inc.B, inc.csr.C, C, &bytes), op);
   Tensor ws = bytes ? alloc_workspace(bytes, x) : Tensor();
-  const bool chunks = inc.C > 0;
+  const bool chunks = inc.csr.C > 0;
   check_status(
       drtk_amd_geometry_laplacian(
           dt, x.data_ptr(), C, inc.vi32.data_ptr<int32_t>(), vi_stride(inc), ptr_or_null(w),
-          w.defined() && w.size(0) > 1 ? inc.F * 3 : 0, inc.crow.data_ptr<int32_t>(), inc.entries.data_ptr<int32_t>(),
-          chunks ? inc.chunk_ptr.data_ptr<int32_t>() : nullptr, chunks ? inc.chunk_begin.data_ptr<int32_t>() : nullptr,
-          chunks ? inc.chunk_row.data_ptr<int32_t>() : nullptr, inc.C, inc.B, N, inc.V, inc.F, out.data_ptr(),
+          w.defined() && w.size(0) > 1 ? inc.F * 3 : 0, inc.csr.crow.data_ptr<int32_t>(), inc.entries.data_ptr<int32_t>(),
+          chunks ? inc.csr.chunk_ptr.data_ptr<int32_t>() : nullptr, chunks ? inc.csr.chunk_begin.data_ptr<int32_t>() : nullptr,
+          chunks ? inc.csr.chunk_row.data_ptr<int32_t>() : nullptr, inc.csr.C, inc.B, N, inc.V, inc.F, out.data_ptr(),
           ws.defined() ? ws.data_ptr() : nullptr, bytes, current_stream(x)),
       op);
   return out;
@@ -753,13 +630,13 @@ Tensor mesh_laplacian_autograd(const Tensor& x, const Tensor& vi, const c10::opt
 std::tuple<Tensor, Tensor> vertex_incidence(const Tensor& vi, int64_t num_vertices) {
   TORCH_CHECK(vi.dim() == 2 || vi.dim() == 3, "vertex_incidence(): expected vi of shape [F,3] or [B,F,3]");
   const Incidence inc = incidence_of(vi, vi.dim() == 3 ? vi.size(0) : 1, num_vertices, "vertex_incidence");
-  return {inc.crow, inc.entries};
+  return {inc.csr.crow, inc.entries};
 }
 std::vector<int64_t> geometry_cache_stats() {
-  return IncidenceCache::instance().stats();
+  return incidence_cache().stats();
 }
 void geometry_cache_clear() {
-  IncidenceCache::instance().clear();
+  incidence_cache().clear();
 }
 
 Tensor3 face_info_cpu(const Tensor&, const Tensor&, bool, bool, bool) {

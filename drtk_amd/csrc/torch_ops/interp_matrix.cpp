@@ -1,6 +1,6 @@
 // interpolate_ext::interpolation_matrix / interpolation_normal_matrix[_values] -- src/interpolate/interpolate_module.cpp
 // :28-310,435-669 -- with the topology-only A^T A pattern built once per face-index tensor and cached.
-#include "common.hpp"
+#include "topology_cache.hpp"
 
 namespace {
 using namespace drtk_amd_torch;
@@ -198,101 +198,18 @@ NormalMatrixPattern build_normal_matrix_pattern(const Tensor& vi, int64_t num_ve
   return out;
 }
 
-// Cache: identity + version of the face-index tensor, as interpolate_module.cpp:36-113 keys it --
-// no content hashing (that would synchronise); an in-place edit bumps the version counter and
-// misses.  Each entry pins its vi so a recycled allocation cannot alias a stale entry; 128 entries, LRU.
-struct TopologyKey {
-  std::array<int64_t, 14> f;
-  bool operator==(const TopologyKey& o) const {
-    return f == o.f;
-  }
-};
-struct TopologyKeyHash {
-  size_t operator()(const TopologyKey& k) const {
-    uint64_t h = 1469598103934665603ull; // FNV-1a over the fields
-    for (int64_t x : k.f) {
-      h ^= static_cast<uint64_t>(x);
-      h *= 1099511628211ull;
-    }
-    return static_cast<size_t>(h);
-  }
-};
-TopologyKey topology_key(const Tensor& vi, int64_t num_vertices) {
-  TopologyKey k;
-  k.f = {static_cast<int64_t>(vi.device().type()),
-         static_cast<int64_t>(vi.device().index()),
-         static_cast<int64_t>(reinterpret_cast<uintptr_t>(vi.storage().unsafeGetStorageImpl())),
-         static_cast<int64_t>(reinterpret_cast<uintptr_t>(vi.data_ptr())),
-         vi.size(0),
-         vi.size(1),
-         vi.size(2),
-         vi.stride(0),
-         vi.stride(1),
-         vi.stride(2),
-         vi.storage_offset(),
-         static_cast<int64_t>(vi.scalar_type()),
-         num_vertices,
-         static_cast<int64_t>(vi.unsafeGetTensorImpl()->version_counter().current_version())};
-  return k;
+// Cached by the identity and version of the face-index tensor, as interpolate_module.cpp:36-113 keys it, and the vertex
+// count (topology_cache.hpp; 128 entries: interpolate_module.cpp:62).
+PinnedLruCache<NormalMatrixPattern>& normal_matrix_pattern_cache() {
+  static PinnedLruCache<NormalMatrixPattern> c;
+  return c;
 }
-
-class NormalMatrixPatternCache {
- public:
-  static constexpr size_t kCapacity = 128; // interpolate_module.cpp:62
-  static NormalMatrixPatternCache& instance() {
-    static NormalMatrixPatternCache c;
-    return c;
-  }
-  NormalMatrixPattern get(const Tensor& vi, int64_t num_vertices) {
-    const TopologyKey key = topology_key(vi, num_vertices);
-    {
-      std::lock_guard<std::mutex> lock(mu_);
-      if (const NormalMatrixPattern* hit = touch(key)) {
-        ++hits_;
-        return *hit;
-      }
-    }
-    // built outside the lock; a racing identical miss is resolved by the second lookup
-    NormalMatrixPattern built = build_normal_matrix_pattern(vi, num_vertices);
-    std::lock_guard<std::mutex> lock(mu_);
-    if (const NormalMatrixPattern* hit = touch(key)) return *hit;
-    ++misses_;
-    while (lru_.size() >= kCapacity) {
-      index_.erase(lru_.back().key);
-      lru_.pop_back();
-    }
-    lru_.push_front(Entry{key, vi, built});
-    index_.emplace(key, lru_.begin());
-    return built;
-  }
-  std::vector<int64_t> stats() {
-    std::lock_guard<std::mutex> lock(mu_);
-    return {hits_, misses_, static_cast<int64_t>(lru_.size())};
-  }
-  void clear() {
-    std::lock_guard<std::mutex> lock(mu_);
-    lru_.clear();
-    index_.clear();
-    hits_ = misses_ = 0;
-  }
-
- private:
-  struct Entry {
-    TopologyKey key;
-    Tensor pinned_vi;
-    NormalMatrixPattern pattern;
-  };
-  const NormalMatrixPattern* touch(const TopologyKey& key) {
-    const auto it = index_.find(key);
-    if (it == index_.end()) return nullptr;
-    lru_.splice(lru_.begin(), lru_, it->second);
-    return &it->second->pattern;
-  }
-  std::mutex mu_;
-  std::list<Entry> lru_;
-  std::unordered_map<TopologyKey, std::list<Entry>::iterator, TopologyKeyHash> index_;
-  int64_t hits_ = 0, misses_ = 0;
-};
+NormalMatrixPattern normal_matrix_pattern_of(const Tensor& vi, int64_t num_vertices) {
+  CacheKey key;
+  append_tensor_identity(key, vi);
+  key.push_back(num_vertices);
+  return normal_matrix_pattern_cache().get(key, vi, [&] { return build_normal_matrix_pattern(vi, num_vertices); });
+}
 
 void normal_matrix_checks(const Tensor& vi, const Tensor& index_img, const Tensor& bary_img) {
   // interpolate_module.cpp:272-301
@@ -326,7 +243,7 @@ Tensor4 normal_matrix_forward_with_pairs(
   normal_matrix_checks(vi, index_img, bary_img);
   TORCH_CHECK(bary_img.is_cuda(), "interpolation_normal_matrix(): drtk_amd implements the MI355X (HIP) path only; got CPU tensors");
   c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(bary_img.device());
-  const NormalMatrixPattern p = NormalMatrixPatternCache::instance().get(vi, num_vertices);
+  const NormalMatrixPattern p = normal_matrix_pattern_of(vi, num_vertices);
   auto values = normal_matrix_values_hip(p.pair_indices, index_img, bary_img, p.col_indices.numel());
   return {p.crow_indices, p.col_indices, values, p.pair_indices};
 }
@@ -342,14 +259,14 @@ Tensor3 normal_matrix_structure_any(const Tensor& vi, int64_t num_vertices) {
   TORCH_CHECK(
       vi.defined() && vi.dtype() == at::kInt && vi.layout() == at::kStrided && vi.dim() == 3 && vi.size(2) == 3,
       "normal_matrix_structure(): expected vi to be a strided int32 tensor of shape [N,F,3]");
-  const NormalMatrixPattern p = NormalMatrixPatternCache::instance().get(vi, num_vertices);
+  const NormalMatrixPattern p = normal_matrix_pattern_of(vi, num_vertices);
   return {p.crow_indices, p.col_indices, p.pair_indices};
 }
 std::vector<int64_t> normal_matrix_cache_stats() {
-  return NormalMatrixPatternCache::instance().stats();
+  return normal_matrix_pattern_cache().stats();
 }
 void normal_matrix_cache_clear() {
-  NormalMatrixPatternCache::instance().clear();
+  normal_matrix_pattern_cache().clear();
 }
 
 Tensor4 interpolation_matrix_cpu(const Tensor&, const Tensor&, const Tensor&) {

@@ -1,13 +1,12 @@
 // drtk_amd_ext::forward_kinematics -- pose to skinning transforms over drtk_amd_kinematics_* (csrc/kinematics.hip): the
 // matrices `skin` reads and the posed joints, and the gradients to the rotations, the rest joints and the root
 // translation, one launch each way.  The SCHEDULE of the parent list (joints by level, children in CSR form) is built on
-// the host with one read of `parents` and cached under geometry.cpp's key rule (tensor identity + version counter, pinned,
-// LRU); a Python sequence is keyed by its contents.
-#include "common.hpp"
-
-#include <hip/hip_runtime_api.h>
+// the host with one read of `parents` and cached (topology_cache.hpp): a tensor by its identity, a Python sequence by its
+// contents, either with the device the schedule lives on.
+#include "topology_cache.hpp"
 
 #include <algorithm>
+#include <array>
 
 namespace {
 using namespace drtk_amd_torch;
@@ -57,65 +56,30 @@ Schedule build_schedule(const std::vector<int64_t>& p, const at::Device& device,
   return s;
 }
 
-// key: [0, ...identity of the tensor...] or [1, ...contents of the sequence...], then the device the schedule lives on
-using ScheduleKey = std::vector<int64_t>;
-struct ScheduleKeyHash {
-  size_t operator()(const ScheduleKey& k) const {
-    uint64_t h = 1469598103934665603ull; // FNV-1a over the fields
-    for (int64_t x : k) {
-      h ^= static_cast<uint64_t>(x);
-      h *= 1099511628211ull;
-    }
-    return static_cast<size_t>(h);
-  }
-};
+PinnedLruCache<Schedule>& schedule_cache() {
+  static PinnedLruCache<Schedule> c;
+  return c;
+}
 
-class ScheduleCache {
- public:
-  static constexpr size_t kCapacity = 128;
-  static ScheduleCache& instance() {
-    static ScheduleCache c;
-    return c;
+// key: [0, ...identity of the tensor...] or [1, ...contents of the sequence...], then the device the schedule lives on
+Schedule schedule_of(const std::optional<Tensor>& pt, at::IntArrayRef pl, const at::Device& device, const char* op) {
+  CacheKey key;
+  if (pt.has_value()) {
+    const Tensor& t = *pt;
+    TORCH_CHECK_VALUE(t.layout() == at::kStrided && t.dim() == 1, op, "(): expected parents of shape [J]");
+    TORCH_CHECK_TYPE(t.scalar_type() == at::kInt || t.scalar_type() == at::kLong, op,
+                     "(): expected parents to be int32 or int64, got ", t.scalar_type());
+    key.push_back(0);
+    append_tensor_identity(key, t);
+  } else {
+    key.reserve(pl.size() + 3);
+    key.push_back(1);
+    key.insert(key.end(), pl.begin(), pl.end());
   }
-  Schedule get(const std::optional<Tensor>& pt, at::IntArrayRef pl, const at::Device& device, const char* op) {
-    ScheduleKey key;
-    if (pt.has_value()) {
-      const Tensor& t = *pt;
-      TORCH_CHECK_VALUE(t.layout() == at::kStrided && t.dim() == 1, op, "(): expected parents of shape [J]");
-      TORCH_CHECK_TYPE(t.scalar_type() == at::kInt || t.scalar_type() == at::kLong, op,
-                       "(): expected parents to be int32 or int64, got ", t.scalar_type());
-      key = {0,
-             static_cast<int64_t>(t.device().type()),
-             static_cast<int64_t>(t.device().index()),
-             static_cast<int64_t>(reinterpret_cast<uintptr_t>(t.storage().unsafeGetStorageImpl())),
-             static_cast<int64_t>(reinterpret_cast<uintptr_t>(t.data_ptr())),
-             t.size(0),
-             t.stride(0),
-             t.storage_offset(),
-             static_cast<int64_t>(t.scalar_type()),
-             static_cast<int64_t>(t.unsafeGetTensorImpl()->version_counter().current_version())};
-    } else {
-      key.reserve(pl.size() + 3);
-      key.push_back(1);
-      key.insert(key.end(), pl.begin(), pl.end());
-    }
-    key.push_back(static_cast<int64_t>(device.type()));
-    key.push_back(static_cast<int64_t>(device.index()));
-    {
-      std::lock_guard<std::mutex> lock(mu_);
-      if (const Schedule* hit = touch(key)) {
-        ++hits_;
-        return *hit;
-      }
-    }
-    if (device.is_cuda()) {
-      // the build reads the parents back and uploads the schedule: not capturable
-      hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-      const hipStream_t s = c10::hip::getCurrentHIPStream(device.index()).stream();
-      TORCH_CHECK(hipStreamIsCapturing(s, &st) != hipSuccess || st == hipStreamCaptureStatusNone, op,
-                  "(): the kinematic schedule of this parent list is not cached yet, and it cannot be built while the "
-                  "stream is being captured -- run the op once with the same parents before the capture");
-    }
+  key.push_back(static_cast<int64_t>(device.type()));
+  key.push_back(static_cast<int64_t>(device.index()));
+  return schedule_cache().get(key, pt.has_value() ? *pt : Tensor(), [&] {
+    check_not_capturing(device, op, "kinematic schedule of this parent list", "parents");
     std::vector<int64_t> p;
     if (pt.has_value()) {
       const Tensor host = pt->detach().to(at::kCPU, at::kLong).contiguous(); // the one host read
@@ -123,46 +87,9 @@ class ScheduleCache {
     } else {
       p.assign(pl.begin(), pl.end());
     }
-    Schedule built = build_schedule(p, device, op);
-    std::lock_guard<std::mutex> lock(mu_);
-    if (const Schedule* hit = touch(key)) return *hit;
-    ++misses_;
-    while (lru_.size() >= kCapacity) {
-      index_.erase(lru_.back().key);
-      lru_.pop_back();
-    }
-    lru_.push_front(Entry{key, pt.has_value() ? *pt : Tensor(), built});
-    index_.emplace(key, lru_.begin());
-    return built;
-  }
-  std::vector<int64_t> stats() {
-    std::lock_guard<std::mutex> lock(mu_);
-    return {hits_, misses_, static_cast<int64_t>(lru_.size())};
-  }
-  void clear() {
-    std::lock_guard<std::mutex> lock(mu_);
-    lru_.clear();
-    index_.clear();
-    hits_ = misses_ = 0;
-  }
-
- private:
-  struct Entry {
-    ScheduleKey key;
-    Tensor pinned_parents;
-    Schedule sched;
-  };
-  const Schedule* touch(const ScheduleKey& key) {
-    const auto it = index_.find(key);
-    if (it == index_.end()) return nullptr;
-    lru_.splice(lru_.begin(), lru_, it->second);
-    return &it->second->sched;
-  }
-  std::mutex mu_;
-  std::list<Entry> lru_;
-  std::unordered_map<ScheduleKey, std::list<Entry>::iterator, ScheduleKeyHash> index_;
-  int64_t hits_ = 0, misses_ = 0;
-};
+    return build_schedule(p, device, op);
+  });
+}
 
 // What the kernels read.  The rotations in place through their strides; the joints as one row [J,3] (c_sN = 0) or N.
 struct FkArgs {
@@ -200,7 +127,7 @@ FkArgs fk_prep(const Tensor& rot, const Tensor& joints_, const std::optional<Ten
                 "(): expected translation on the device and in the dtype of rotations");
     a.tr = tr->contiguous();
   }
-  a.sched = ScheduleCache::instance().get(pt, pl, rot.device(), op);
+  a.sched = schedule_of(pt, pl, rot.device(), op);
   TORCH_CHECK_VALUE(a.sched.J == a.J, op, "(): expected parents of length J = ", a.J, ", got ", a.sched.J);
   return a;
 }
@@ -294,16 +221,16 @@ std::tuple<Tensor, Tensor> fk_cpu(const Tensor&, const Tensor&, const std::optio
 std::tuple<Tensor, Tensor, Tensor, Tensor> kinematic_schedule(const std::optional<Tensor>& pt, at::IntArrayRef pl, int64_t device_index) {
   const at::Device device(at::kCUDA, static_cast<c10::DeviceIndex>(device_index));
   c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(device);
-  const Schedule s = ScheduleCache::instance().get(pt, pl, device, "kinematic_schedule");
+  const Schedule s = schedule_of(pt, pl, device, "kinematic_schedule");
   const int64_t J = s.J, D = s.D;
   return {s.pack.narrow(0, J, J), s.pack.narrow(0, 2 * J, D + 1), s.pack.narrow(0, 2 * J + D + 1, J + 1),
           s.pack.narrow(0, 3 * J + D + 2, J - s.roots)};
 }
 std::vector<int64_t> kinematics_cache_stats() {
-  return ScheduleCache::instance().stats();
+  return schedule_cache().stats();
 }
 void kinematics_cache_clear() {
-  ScheduleCache::instance().clear();
+  schedule_cache().clear();
 }
 
 } // namespace

@@ -1,5 +1,6 @@
 // drtk_amd_ext::shade -- Blinn-Phong deferred shading of an interpolated G-buffer, over drtk_amd_shade_forward /
 // drtk_amd_shade_backward (include/drtk_amd.h).  No reference counterpart.  Host-only C++; the CPU key raises.
+#include <array>
 #include <cmath>
 
 #include "common.hpp"
