@@ -37,6 +37,7 @@ from drtk_amd.kinematics import forward_kinematics  # noqa: F401
 from drtk_amd.mipmap_grid_sample import mipmap_grid_sample  # noqa: F401
 from drtk_amd.mipmap_pyramid import mipmap_pyramid  # noqa: F401
 from drtk_amd.msi import msi  # noqa: F401
+from drtk_amd.nearest import chamfer_distance, nearest_points  # noqa: F401
 from drtk_amd.rasterize import (  # noqa: F401
     get_depth_order,
     rasterize,
@@ -71,8 +72,10 @@ __version__ = "0.1.0"
 # step from rig parameters to geometry: forward and the gradients to the rest pose, the weights and the joint transforms,
 # no float atomics) with its companion `sparse_skin_weights` is one more, and stays out of the drop-in too.
 # `forward_kinematics` (the step before it: axis-angle or matrix pose along a joint tree to the skinning matrices `skin`
-# reads and the posed joints, one launch each way, the exponential map smooth at 0) is the latest, and stays out of the
-# drop-in as well.  `transform` / `transform_with_v_cam` serve the pinhole camera and, on the HIP device, the reference's
+# reads and the posed joints, one launch each way, the exponential map smooth at 0) is one more, and stays out of the
+# drop-in as well.  `nearest_points` / `chamfer_distance` (closest-point queries between point sets by a brute-force tiled
+# kernel, bit-defined, with the gradients to both sets in a fixed order: the data term of registration to a scan) are the
+# latest, and stay out of the drop-in too.  `transform` / `transform_with_v_cam` serve the pinhole camera and, on the HIP device, the reference's
 # distortion models (radial-tangential, fisheye, fisheye62 with its lookup table, per-view lists) in one fused kernel each
 # way; the field-of-view estimators live in drtk_amd.transform (`estimate_rt_fov`, `estimate_fisheye_fov`,
 # `estimate_fisheye62_fov`) and in the drop-in's drtk.utils.  Not provided: the pure-PyTorch `*_ref` models (out of scope).
@@ -119,4 +122,6 @@ __all__ = [
     "skin",
     "sparse_skin_weights",
     "forward_kinematics",
+    "nearest_points",
+    "chamfer_distance",
 ]

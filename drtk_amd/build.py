@@ -24,7 +24,7 @@ INC = os.path.join(ROOT, "include")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
-KERNEL_SRCS = ["rasterize.hip", "rasterize_lines.hip", "render.hip", "interpolate.hip", "edge_grad.hip", "transform.hip", "transform_distort.hip", "interp_matrix.hip", "mipmap.hip", "uv_derivative.hip", "geometry.hip", "grid_scatter.hip", "msi.hip", "filter2d.hip", "composite.hip", "mipmap_pyramid.hip", "image_loss.hip", "shade.hip", "skin.hip", "kinematics.hip", "capi.hip"]
+KERNEL_SRCS = ["rasterize.hip", "rasterize_lines.hip", "render.hip", "interpolate.hip", "edge_grad.hip", "transform.hip", "transform_distort.hip", "interp_matrix.hip", "mipmap.hip", "uv_derivative.hip", "geometry.hip", "grid_scatter.hip", "msi.hip", "filter2d.hip", "composite.hip", "mipmap_pyramid.hip", "image_loss.hip", "shade.hip", "skin.hip", "kinematics.hip", "nearest.hip", "capi.hip"]
 HEADERS = ["common.hpp", "segscatter.hpp", "grid_coords.hpp"]
 LIB = os.path.join(PKG, "libdrtk_amd.so")
 OPS = os.path.join(PKG, "drtk_amd_torch_ops.so")
@@ -167,7 +167,7 @@ def build_variant(out, defines, verbose=True):
 
 
 OPS_DIR = os.path.join(CSRC, "torch_ops")
-OPS_SRCS = ["rasterize.cpp", "render.cpp", "interpolate.cpp", "interp_matrix.cpp", "mipmap.cpp", "edge_grad.cpp", "transform.cpp", "geometry.cpp", "grid_scatter.cpp", "msi.cpp", "filter2d.cpp", "composite.cpp", "mipmap_pyramid.cpp", "image_loss.cpp", "shade.cpp", "skin.cpp", "kinematics.cpp"]
+OPS_SRCS = ["rasterize.cpp", "render.cpp", "interpolate.cpp", "interp_matrix.cpp", "mipmap.cpp", "edge_grad.cpp", "transform.cpp", "geometry.cpp", "grid_scatter.cpp", "msi.cpp", "filter2d.cpp", "composite.cpp", "mipmap_pyramid.cpp", "image_loss.cpp", "shade.cpp", "skin.cpp", "kinematics.cpp", "nearest.cpp"]
 
 
 def _ops_deps():

@@ -185,6 +185,10 @@ EXPORTS = [
     "drtk_amd_kinematics_forward",
     "drtk_amd_kinematics_backward_workspace_bytes",
     "drtk_amd_kinematics_backward",
+    "drtk_amd_nearest_forward_workspace_bytes",
+    "drtk_amd_nearest_forward",
+    "drtk_amd_nearest_backward_workspace_bytes",
+    "drtk_amd_nearest_backward",
     "drtk_amd_selftest_exact_div",
     "drtk_amd_kernel_timing_begin",
     "drtk_amd_kernel_timing_report",
@@ -1482,6 +1486,108 @@ def kinematics_backward(grad_transforms, grad_posed, rotations, joints, schedule
             _p(ws), ctypes.c_size_t(need), _stream(rotations, stream)),
         "kinematics_backward")
     return gr, gc, gt
+
+
+# DRTK_NEAREST_* of include/drtk_amd.h
+NEAREST_R = 4
+NEAREST_QUERIES = 1024
+NEAREST_TILE = 1024
+NEAREST_SPLIT_BLOCKS = 512
+NEAREST_CHUNK = 256
+
+
+def nearest_split(N, P, M) -> Tuple[int, int]:
+    """(S, L) of the launch rule of drtk_amd_nearest_forward (include/drtk_amd.h): S ranges of L targets."""
+    cd = lambda a, b: -(-a // b)  # noqa: E731
+    B = N * cd(P, NEAREST_QUERIES)
+    if B <= 0 or B >= NEAREST_SPLIT_BLOCKS or M <= NEAREST_TILE:
+        return 1, M
+    S0 = min(cd(NEAREST_SPLIT_BLOCKS, B), cd(M, NEAREST_TILE))
+    L = cd(cd(M, S0), NEAREST_TILE) * NEAREST_TILE
+    return cd(M, L), L
+
+
+def _points(t):
+    """-> (tensor read in place or copied, sN, sP, B, count) of points [B,count,3] / [count,3], B = 1 or N"""
+    assert t.dim() in (2, 3) and t.shape[-1] == 3
+    t = t[None] if t.dim() == 2 else t
+    if t.shape[0] > 1 and t.stride(0) == 0:
+        t = t[:1]
+    B, count = t.shape[0], t.shape[1]
+    s = t.stride()
+    if not (s[2] == 1 and (count <= 1 or s[1] >= 3) and (B <= 1 or s[0] >= (count - 1) * (s[1] if count > 1 else 0) + 3)):
+        t = t.contiguous()
+    return t, (t.stride(0) if B > 1 else 0), (t.stride(1) if count > 1 else 3), B, count
+
+
+def _nearest_args(p, q):
+    assert p.dtype == q.dtype and p.device == q.device
+    N = max((p.shape[0] if p.dim() == 3 else 1), (q.shape[0] if q.dim() == 3 else 1))
+    p, p_sN, p_sP, pB, P = _points(p)
+    q, q_sN, q_sM, qB, M = _points(q)
+    assert pB in (1, N) and qB in (1, N)
+    return p, p_sN, p_sP, q, q_sN, q_sM, N, P, M
+
+
+def nearest_forward_workspace_bytes(dtype, N, P, M) -> int:
+    out = ctypes.c_size_t(0)
+    code = DRTK_F32 if dtype == th.float32 else DRTK_F64
+    _check(lib().drtk_amd_nearest_forward_workspace_bytes(ctypes.c_int(code), _i(N), _i(P), _i(M), ctypes.byref(out)),
+           "nearest_forward")
+    return out.value
+
+
+def nearest_backward_workspace_bytes(dtype, N, P, M, need_grad_q=True) -> int:
+    out = ctypes.c_size_t(0)
+    code = DRTK_F32 if dtype == th.float32 else DRTK_F64
+    _check(lib().drtk_amd_nearest_backward_workspace_bytes(ctypes.c_int(code), _i(N), _i(P), _i(M),
+                                                           ctypes.c_int(int(need_grad_q)), ctypes.byref(out)), "nearest_backward")
+    return out.value
+
+
+@_on_tensor_device
+def nearest_forward(p, q, stream=None):
+    """(dist2 [N,P], idx int32 [N,P]) of p [N,P,3] / [1,P,3] / [P,3] and q likewise (N the larger batch); a `[..., :3]`
+    view of a wider tensor is read in place."""
+    p, p_sN, p_sP, q, q_sN, q_sM, N, P, M = _nearest_args(p, q)
+    dist2 = _out(N, P, dtype=p.dtype, device=p.device)
+    idx = _out(N, P, dtype=th.int32, device=p.device)
+    need = nearest_forward_workspace_bytes(p.dtype, N, P, M)
+    ws = _out(need, dtype=th.uint8, device=p.device) if need else None
+    assert ws is None or ws.data_ptr() % 8 == 0
+    _check(lib().drtk_amd_nearest_forward(ctypes.c_int(_dt(p)), _p(p), _i(p_sN), _i(p_sP), _p(q), _i(q_sN), _i(q_sM), _i(N),
+                                          _i(P), _i(M), _p(dist2), _p(idx), _p(ws), ctypes.c_size_t(need), _stream(p, stream)),
+           "nearest_forward")
+    return dist2, idx
+
+
+@_on_tensor_device
+def nearest_backward(grad_dist2, p, q, idx, order=None, grads=("p", "q"), stream=None):
+    """(grad_p, grad_q) of nearest_forward, None for what `grads` does not name; each has the batch of its input (1: the
+    views added).  `order`: int32 [N,P], per view the STABLE ascending argsort of idx (needed for "q"; made here with
+    torch's stable sort when not given)."""
+    pB = p.shape[0] if p.dim() == 3 else 1
+    qB = q.shape[0] if q.dim() == 3 else 1
+    p, p_sN, p_sP, q, q_sN, q_sM, N, P, M = _nearest_args(p, q)
+    g = grad_dist2.contiguous()
+    idx = idx.contiguous()
+    assert g.shape == (N, P) and g.dtype == p.dtype and idx.shape == (N, P) and idx.dtype == th.int32
+    gp = _out(pB, P, 3, dtype=p.dtype, device=p.device) if "p" in grads else None
+    gq = ws = None
+    need = 0
+    if "q" in grads:
+        gq = _out(qB, M, 3, dtype=p.dtype, device=p.device)
+        if order is None:
+            order = th.sort(idx, dim=1, stable=True).indices
+        order = order.to(th.int32).contiguous()
+        assert order.shape == (N, P)
+        need = nearest_backward_workspace_bytes(p.dtype, N, P, M)
+        ws = _out(max(need, 1), dtype=th.uint8, device=p.device)
+        assert ws.data_ptr() % 8 == 0
+    _check(lib().drtk_amd_nearest_backward(ctypes.c_int(_dt(p)), _p(g), _p(p), _i(p_sN), _i(p_sP), _p(q), _i(q_sN), _i(q_sM),
+                                           _p(idx), _p(order), _i(N), _i(P), _i(M), _i(pB), _p(gp), _i(qB), _p(gq), _p(ws),
+                                           ctypes.c_size_t(need), _stream(p, stream)), "nearest_backward")
+    return gp, gq
 
 
 def edge_grad_backward_workspace_bytes(dtype, N, H, W) -> int:

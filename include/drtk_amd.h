@@ -827,6 +827,65 @@ int drtk_amd_kinematics_backward(
     const int32_t* child_entries, int64_t N, int64_t J, void* grad_rotations, int64_t grad_joints_B, void* grad_joints,
     void* grad_translation, void* workspace, size_t workspace_bytes, drtk_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Closest-point queries (no counterpart in the reference's library): for every query point p[n,i] the nearest of the
+ * view's targets q[n,0..M-1] by brute force, and the gradients of the squared distance, without atomics.
+ *
+ * Definition, which the kernels produce bit for bit (every operation rounded in `dtype`, in this association, no
+ * contraction):
+ *     d2(i,j) = ((px-qx)*(px-qx) + (py-qy)*(py-qy)) + (pz-qz)*(pz-qz)
+ *     idx[n,i] = the LOWEST j whose d2 is minimal among the candidates with d2 < +inf;  dist2[n,i] = that d2.
+ * A candidate whose d2 is NaN or +inf (a NaN coordinate, an overflowing square) is never chosen; with no candidate left
+ * (M = 0, a NaN query, every candidate rejected) idx = -1 and dist2 = +inf.
+ *
+ * Shapes: point i of view n of p is the 3 consecutive elements at n*p_sN + i*p_sP (p_sP >= 3: 3 for [N,P,3], 4 or 6 for the
+ * leading three columns of an [N,P,4] / [N,P,6] tensor read in place; p_sN = 0: one set of points shared by the views,
+ * else >= (P-1)*p_sP + 3); q likewise with q_sN, q_sM.  dist2 [N,P] in `dtype`, idx [N,P] int32, contiguous.
+ * N >= 0, 0 <= P, M < 2^31.
+ *
+ * Launch rule.  A workgroup of 256 lanes holds DRTK_NEAREST_QUERIES = 256 * DRTK_NEAREST_R queries of one view in
+ * registers (DRTK_NEAREST_R per lane) and walks the targets in LDS tiles of DRTK_NEAREST_TILE, j ascending, keeping the
+ * minimum with a strict `<`.  B = N * ceil(P / DRTK_NEAREST_QUERIES) workgroups cover the queries.  When
+ * B < DRTK_NEAREST_SPLIT_BLOCKS (twice the 256 compute units of the card) and M > DRTK_NEAREST_TILE, the targets are split
+ * into S contiguous ranges, one workgroup per (queries, range):
+ *     S0 = min(ceil(DRTK_NEAREST_SPLIT_BLOCKS / B), ceil(M / DRTK_NEAREST_TILE))
+ *     L  = ceil(ceil(M / S0) / DRTK_NEAREST_TILE) * DRTK_NEAREST_TILE        (targets per range, whole tiles)
+ *     S  = ceil(M / L)                                                       (the last range may be short)
+ * otherwise S = 1.  With S > 1 every range writes its (d2, idx) to the workspace ([N,S,P] of `dtype`, then [N,S,P] int32)
+ * and a merge launch takes them in ascending range order with a strict `<`; with S = 1 the outputs are written directly
+ * and the workspace is not touched: _forward_workspace_bytes is N*S*P*(sizeof(dtype) + 4) for S > 1 and 0 for S = 1.  The
+ * rule depends on the sizes alone and the results do not depend on it.  Workspaces are 8-byte aligned.
+ *
+ * nearest_backward: grad_dist2 [N,P], idx as the forward wrote it.  NULL outputs are skipped, at least one must be given.
+ *   grad_p [grad_p_B,P,3], grad_p_B = N or 1:  2 g[n,i] (p_i - q_idx), exactly 0 where idx = -1; grad_p_B = 1: the views'
+ *     rows added in ascending n in double.
+ *   grad_q [grad_q_B,M,3], grad_q_B = N or 1:  - sum over the i with idx[n,i] = j of 2 g[n,i] (p_i - q_j), every term and
+ *     the sum in double, rounded once; exactly 0 for a target nobody chose; grad_q_B = 1: the views added in ascending n.
+ *     It needs `order` int32 [N,P]: per view the STABLE ascending argsort of idx[n,:] (equal indices keep ascending i; the
+ *     -1 rows come first and are skipped), built by the caller (drtk_amd_ext::nearest_points sorts on the device), and
+ *     the workspace of _backward_workspace_bytes (0 without grad_q; else N*P*(3*8 + 4) bytes rounded up to 8).
+ *     Order of the sum: the sorted list of a view is cut into chunks of DRTK_NEAREST_CHUNK positions; within a chunk the
+ *     terms of one target are added in ascending sorted position; a target's chunk sums are added in ascending chunk
+ *     order; shared targets then add the views in ascending n.  A second launch, one lane per target, finds the target's
+ *     run by bisection, adds its chunk sums and is the only writer of grad_q (zeros included).
+ * Results are bitwise reproducible; each gradient requested alone has the bits it has when both are requested.
+ */
+#define DRTK_NEAREST_R 4
+#define DRTK_NEAREST_QUERIES 1024
+#define DRTK_NEAREST_TILE 1024
+#define DRTK_NEAREST_SPLIT_BLOCKS 512
+#define DRTK_NEAREST_CHUNK 256
+int drtk_amd_nearest_forward_workspace_bytes(drtk_dtype_t dtype, int64_t N, int64_t P, int64_t M, size_t* bytes);
+int drtk_amd_nearest_forward(
+    drtk_dtype_t dtype, const void* p, int64_t p_sN, int64_t p_sP, const void* q, int64_t q_sN, int64_t q_sM, int64_t N,
+    int64_t P, int64_t M, void* dist2, int32_t* idx, void* workspace, size_t workspace_bytes, drtk_stream_t stream);
+int drtk_amd_nearest_backward_workspace_bytes(drtk_dtype_t dtype, int64_t N, int64_t P, int64_t M, int need_grad_q,
+                                              size_t* bytes);
+int drtk_amd_nearest_backward(
+    drtk_dtype_t dtype, const void* grad_dist2, const void* p, int64_t p_sN, int64_t p_sP, const void* q, int64_t q_sN,
+    int64_t q_sM, const int32_t* idx, const int32_t* order, int64_t N, int64_t P, int64_t M, int64_t grad_p_B, void* grad_p,
+    int64_t grad_q_B, void* grad_q, void* workspace, size_t workspace_bytes, drtk_stream_t stream);
+
 /* Diagnostics: compares the rasterizer's reciprocal-based exact division with the IEEE `/` on `count`
  * pseudo-random operand pairs on the device; *d_mismatches (device memory) receives the number of
  * differing results (must be 0). */
